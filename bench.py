@@ -8,8 +8,13 @@ global-norm clip 0.5, entropy 0.01, value coef 0.5). One timed step = one full A
 value, n-step returns, the learner forward/loss/backward over the 160-sample batch and the fused RMSprop update
 (and, for N > 1, the RCCL all-reduce of the flat gradient slab). Weak scaling: 32 envs per GPU.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]; N > 1 under torch.distributed.run (one rank per GPU).
-Synthetic data (the Pong-shaped env bank renders its own frames), random-init weights.
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]; N > 1 under
+torch.distributed.run (one rank per GPU). Synthetic data (the Pong-shaped env bank renders its own frames), random-init
+weights; both are seeded by the preset, so the same arguments give the same inputs in every run.
+
+A plain run sets up, warms up, times the K updates and prints the result line: that is all the headline needs, and
+this benchmark measures nothing else, so ``--full`` (the switch for every further measurement) adds nothing here.
+``--dump-outputs DIR`` writes what the last timed update left for its caller as ``DIR/<name>.npy`` (float32).
 """
 from __future__ import annotations
 
@@ -39,6 +44,17 @@ def _json_stdout():
     return out
 
 
+def dump_outputs(tr, outdir):
+    """What one update leaves for the trainer's caller: the updated fp32 parameter slab, the loss statistics and the
+    rollout it learned from (6.8 MB for the headline model, all of it written)."""
+    import numpy as np
+    st = tr.storage
+    os.makedirs(outdir, exist_ok=True)
+    for name, t in (("params", tr.flat.data), ("stats", tr.stats_buf), ("actions", st.actions),
+                    ("rewards", st.rewards), ("dones", st.dones), ("values", st.values)):
+        np.save(os.path.join(outdir, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def main():
     out_fd = _json_stdout()
     ap = argparse.ArgumentParser()
@@ -60,6 +76,12 @@ def main():
                     help="one process: run the data-parallel schedule (--overlap, --bucket-dtype) on a 1-rank RCCL "
                          "group, so its collectives and buckets are issued exactly as at N >= 2 (the step from N = 1 "
                          "to N = 2 of a scaling curve, without the second GPU)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed updates write what the last one left (parameters, loss statistics, the "
+                         "rollout's actions / rewards / dones / values) as DIR/<name>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure (this benchmark has none: the other "
+                         "configurations live in scripts/bench_configs.py)")
     args = ap.parse_args()
 
     from actor_critic_algs_on_tensorflow_amd import preset
@@ -102,6 +124,8 @@ def main():
         dt = float(t)
     steps_per_update = cfg.n_steps * args.envs * world
     value = steps_per_update * args.steps / dt
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(tr, args.dump_outputs)
     if rank == 0:
         out = {
             "metric": METRIC,

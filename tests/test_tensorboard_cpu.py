@@ -42,9 +42,12 @@ def test_seg_stats_cpu_matches_float64():
         assert np.allclose(st[i].tolist(), want, rtol=1e-6, atol=1e-7)
 
 
-def test_basic_ac_writes_reference_tags(tmp_path):
+def test_basic_ac_writes_reference_tags(tmp_path, monkeypatch):
     from actor_critic_algs_on_tensorflow_amd.api import train
-    out = str(tmp_path / "log.txt")
+    # a relative outdir inside tmp_path: summaries_dir cuts the outdir at its FIRST '.', as the reference does, so an
+    # absolute one would leave tb_root wherever a parent directory of tmp_path has a dot in its name
+    monkeypatch.chdir(tmp_path)
+    out = "log.txt"
     r = train("basic_ac", env="CartPole-v0", total_updates=2, outdir=out, quiet=True, save_every=0,
               checkpoint_dir=None, ep_length_stop=200, tboard=True, tb_root=str(tmp_path))
     files = glob.glob(os.path.join(TB.summaries_dir(out, str(tmp_path)), "events.out.tfevents.*"))
@@ -64,10 +67,11 @@ def test_basic_ac_writes_reference_tags(tmp_path):
     assert abs(last["Actor/stddev_8/max"] - wk.max().item()) < 1e-6
 
 
-def test_vectorised_trainer_tboard_and_phase_timers(tmp_path):
+def test_vectorised_trainer_tboard_and_phase_timers(tmp_path, monkeypatch):
     from actor_critic_algs_on_tensorflow_amd import preset
     from actor_critic_algs_on_tensorflow_amd.algos.trainer import ActorCriticTrainer
-    out = str(tmp_path / "run.txt")
+    monkeypatch.chdir(tmp_path)   # relative outdir, see test_basic_ac_writes_reference_tags
+    out = "run.txt"
     metrics = str(tmp_path / "m.jsonl")
     tr = ActorCriticTrainer(preset("mujoco_ppo_dp8", num_envs=4, n_steps=8, ppo_minibatches=2, ppo_epochs=1,
                                    device="cpu", cuda_graph=False, outdir=out, quiet=True, stdout_freq=1,
