@@ -1,9 +1,11 @@
 // torch.ops.acamd.* registrations for the gfx950 kernels in csrc/kernels/*.hip.
 //
-// The kernels are compiled by hipcc without torch headers and export plain C launchers taking raw pointers and a
-// hipStream_t; this file (the only one that includes torch) validates tensors, resolves the current HIP stream of
-// torch.cuda (so ops are hipGraph-capturable) and forwards. Every op mutates its output arguments in place and
-// returns nothing: the Python layer owns all buffers (static addresses for graph capture).
+// The kernels are compiled by hipcc without torch headers and export plain C launchers, declared once in
+// kernels/launch_api.h (included by both sides, so the compiler checks every signature). This file (the only one that
+// includes torch) validates tensors, fills the launcher's argument block by field name (kernels/*_args.h), resolves
+// the current HIP stream of torch.cuda (so ops are hipGraph-capturable) and forwards. Operand groups that several ops
+// share (env bank, policy head, fc planes, conv trunk) have one checked constructor each. Every op mutates its output
+// arguments in place and returns nothing: the Python layer owns all buffers (static addresses for graph capture).
 #include <ATen/ATen.h>
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
@@ -15,132 +17,7 @@
 #include <cstring>
 #include <vector>
 
-#include "gemm_desc.h"
-#include "mlp_desc.h"
-#include "ppo_head.h"
-
-extern "C" {
-hipError_t aca_seg_stats(const float*, const int64_t*, int, float*, hipStream_t);
-hipError_t aca_colsum_reduce(const float*, int, int, float*, int, hipStream_t);
-hipError_t aca_mlp_tshadow(const aca::MlpTower*, int, int, hipStream_t);
-hipError_t aca_opt_multi(const int64_t*, const float*, const int64_t*, int, int, float, float, float, int, int,
-                         hipStream_t);
-hipError_t aca_prp_perm(int64_t*, int, uint32_t, const int64_t*, int, hipStream_t);
-hipError_t aca_mlp_fwd(const aca::MlpArgs*, int, size_t, int, hipStream_t);
-hipError_t aca_mlp_wgrad(const aca::WgradArgs*, hipStream_t);
-hipError_t aca_mlp_epoch_gather(const aca::EpochGatherArgs*, hipStream_t);
-hipError_t aca_ppo_head(const aca::PpoHeadArgs*, int, hipStream_t);
-int aca_ppo_head_planes(int);
-int aca_opt_set_unroll(int);
-void aca_opt_set_stamps(int64_t*);
-hipError_t aca_fc_bwd(const uint16_t*, const uint16_t*, const uint16_t*, uint16_t*, float*, int, float*, uint64_t*,
-                      hipStream_t);
-hipError_t aca_fc_rollout(const uint16_t*, int64_t, int, const uint16_t*, int, int, float*, int64_t, int, int, int*,
-                          unsigned long long*, int, hipStream_t);
-hipError_t aca_mlp_rollout(const aca::RolloutArgs*, size_t, hipStream_t);
-hipError_t aca_env_step_cartpole(float*, int32_t*, int64_t*, float*, float*, const int64_t*, const int32_t*,
-                                 const float*, float*, float*, uint8_t*, uint8_t*, uint32_t, int, int, int, float*,
-                                 hipStream_t);
-hipError_t aca_env_step_pendulum(float*, int32_t*, int64_t*, float*, float*, const int64_t*, const float*, int,
-                                 const float*, float*, float*, uint8_t*, uint8_t*, uint32_t, int, int, int, float*,
-                                 hipStream_t);
-hipError_t aca_env_step_linear(float*, int32_t*, int64_t*, float*, float*, const int64_t*, const float*,
-                               const float*, const float*, const float*, float*, float*, uint8_t*, uint8_t*,
-                               uint32_t, int, int, int, float*, hipStream_t);
-hipError_t aca_env_step_pong(float*, int32_t*, int64_t*, float*, float*, const int64_t*, const int32_t*,
-                             const uint8_t*, uint8_t*, float*, uint8_t*, uint8_t*, uint32_t, int, int, int,
-                             hipStream_t);
-hipError_t aca_fc_value(const float*, int, int64_t, const float*, const uint16_t*, int, const float*, float*,
-                        uint16_t*, int, hipStream_t);
-hipError_t aca_env_policy_step_pong(uint16_t*, const float*, int, int64_t, const float*, int, const uint16_t*,
-                                    const float*, int, float*, int32_t*,
-                                    float*, float*, float*, int, uint32_t, float*, int32_t*, int64_t*, float*, float*,
-                                    const int64_t*, const uint8_t*, uint8_t*, float*, uint8_t*, uint8_t*, uint32_t,
-                                    int, int, int, int, uint64_t*, hipStream_t);
-hipError_t aca_pong_fused_step(uint16_t*, const float*, int, int64_t, const float*, const uint16_t*, const float*, int,
-                               float*, int32_t*, float*, float*, float*, int, uint32_t, float*, int32_t*, int64_t*,
-                               float*, float*, int32_t*, int64_t*, float*, float*, const int64_t*, const uint8_t*,
-                               uint8_t*, float*, uint8_t*, uint8_t*, uint32_t, int, const uint16_t*, const float*,
-                               const uint16_t*, const float*, const uint16_t*, const float*, uint16_t*, uint16_t*,
-                               uint16_t*, float, uint8_t*, uint64_t*, int, int, hipStream_t);
-hipError_t aca_pong_fused_env_step(uint16_t*, const float*, int, int64_t, const float*, const uint16_t*, const float*,
-                                   int, float*, int32_t*, float*, float*, float*, int, uint32_t, float*, int32_t*,
-                                   int64_t*, float*, float*, const int64_t*, uint8_t*, float*, uint8_t*, uint8_t*,
-                                   uint32_t, int, const uint16_t*, const float*, const uint16_t*, const float*,
-                                   const uint16_t*, const float*, uint16_t*, uint16_t*, uint16_t*, float, uint8_t*,
-                                   float*, int32_t*, int64_t*, float*, uint64_t*, int, int, hipStream_t);
-hipError_t aca_wave_reduce_check(const float*, float*, int, hipStream_t);
-hipError_t aca_categorical_sample(const float*, int, int, int, const int64_t*, const int64_t*, const int64_t*, int,
-                                  uint32_t, int32_t*, float*, float*, float*, hipStream_t);
-hipError_t aca_ev(const float*, const float*, float*, int, hipStream_t);
-hipError_t aca_gaussian_sample(const float*, int, int, int, const float*, const int64_t*, uint32_t, float*, float*,
-                               float*, hipStream_t);
-hipError_t aca_gae(const float*, const float*, const uint8_t*, float*, float*, int, int, float, float, hipStream_t);
-hipError_t aca_nstep(const float*, const float*, const uint8_t*, float*, float*, int, int, float, int, hipStream_t);
-hipError_t aca_normalize(const float*, float*, int, float, hipStream_t);
-hipError_t aca_moments(const float*, const float*, float*, int, hipStream_t);
-void aca_returns_scan_geometry(int, int, int*, int*, int*, int*);
-hipError_t aca_returns_scan(const float*, const float*, const uint8_t*, float*, float*, double*, double*, unsigned int*,
-                            double*, float*, int, int, int, int, int, float, float, float, hipStream_t);
-hipError_t aca_normalize_mom(const float*, float*, const double*, int, float, hipStream_t);
-int aca_ev_multi_blocks(int);
-hipError_t aca_gemm_group_run(const AcaGemmDesc*, int, hipStream_t, int*);
-hipError_t aca_mb_gather(const uint8_t*, int64_t, const int*, const float*, const float*, const float*, const float*,
-                         uint8_t*, int*, float*, float*, float*, float*, int, int, uint32_t, int64_t*, int, int,
-                         const double*, float, unsigned int*, int64_t*, hipStream_t);
-hipError_t aca_ev_multi(const float*, const float*, float*, int, double*, unsigned int*, hipStream_t);
-hipError_t aca_conv1_wgrad2(const uint8_t*, const uint16_t*, float*, int, int, float, const int64_t*, hipStream_t);
-hipError_t aca_conv_wgrad_gemm(int, const uint16_t*, const uint16_t*, float*, int, int, hipStream_t);
-hipError_t aca_gemm_big(const AcaGemmDesc*, hipStream_t);
-int64_t aca_gemm_big_ws(int, int, int);
-hipError_t aca_sumsq(const void*, size_t, float*, int, hipStream_t);
-hipError_t aca_sumsq_multi(const float* const*, const size_t*, float* const*, int, hipStream_t);
-int aca_sumsq_parts();
-hipError_t aca_adam_step(float*, float*, float*, float*, size_t, const float*, float*, const float*, float*, uint16_t*,
-                         float, float, float, float, float, unsigned int*, int, float, float, const int64_t*,
-                         const uint16_t*, hipStream_t);
-hipError_t aca_rmsprop_step(float*, float*, float*, size_t, const float*, const float*, float*, uint16_t*, float, float,
-                            float, float, int, float, float, const int64_t*, const uint16_t*, hipStream_t);
-hipError_t aca_cast_bf16(const float*, uint16_t*, size_t, hipStream_t);
-hipError_t aca_grad_move(float*, float*, size_t, int*, int, hipStream_t);
-hipError_t aca_gemm_run(const AcaGemmDesc*, hipStream_t);
-int aca_gemm_effective_splits(int, int, int);
-int aca_gemm_tile_dims(int, int*, int*);
-int aca_gemm_supported(int, int);
-hipError_t aca_im2col_u8_nchw(const uint8_t*, uint16_t*, int, int, int, int, int, int, int, float, hipStream_t);
-hipError_t aca_im2col_nhwc(const uint16_t*, uint16_t*, int, int, int, int, int, int, int, hipStream_t);
-hipError_t aca_col2im_nhwc(const uint16_t*, const uint16_t*, uint16_t*, float*, int, int, int, int, int, int, int,
-                           hipStream_t);
-hipError_t aca_colsum_bf16(const uint16_t*, int64_t, int, int64_t, float*, hipStream_t);
-hipError_t aca_ac_loss(const float*, int64_t, const float*, int64_t, const int32_t*, const float*, const float*,
-                       const float*, const float*, const float*, const float*, const float*, const float*, float, float,
-                       float, uint16_t*, int64_t, uint16_t*, int64_t, float*, float*, int, int, int, int,
-                       const float*, const float*, const uint8_t*, int, int, int, float, float, int, float*, float*,
-                       float*, int, hipStream_t);
-hipError_t aca_cnn_trunk_fwd_s16(const uint8_t*, const uint16_t*, const float*, const uint16_t*, const float*,
-                                 const uint16_t*, const float*, uint16_t*, uint16_t*, uint16_t*, int, float, uint8_t*,
-                                 const int64_t*, int, hipStream_t);
-hipError_t aca_grad_finalize(const int64_t*, int, float*, const double*, int, int, const float*, const float*, float*,
-                             int, hipStream_t);
-hipError_t aca_a2c_head_env(const float*, const int32_t*, const float*, const float*, const float*, float,
-                            const float*, float*, const uint8_t*, int, int, int, int, float, float, float*, float*,
-                            const uint16_t*, const uint16_t*, uint16_t*, int, const float*, int, int64_t,
-                            const float*, const float*, float*, float*, float*, double*, uint64_t*, hipStream_t);
-hipError_t aca_head_bwd(const float*, const int32_t*, const float*, const float*, const float*, float, const float*,
-                        const float*, const uint8_t*, int, int, int, int, int, float, float, float*, float*,
-                        const uint16_t*, const uint16_t*, uint16_t*, float*, float*, float*, float*, int,
-                        uint64_t*, hipStream_t);
-hipError_t aca_a2c_head(const float*, const int32_t*, const float*, const float*, const float*, float, const float*,
-                        float*, const uint8_t*, int, int, int, int, int, float, float, float*, float*,
-                        const uint16_t*, const uint16_t*, uint16_t*, float*, float*, float*, float*, int,
-                        const float*, int, int64_t, const float*, const float*, unsigned int*, uint64_t*, hipStream_t);
-hipError_t aca_cnn_trunk_bwd(const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*, const uint16_t*,
-                             uint16_t*, uint16_t*, float*, int, uint64_t*, int, const uint8_t*, const int64_t*, float*,
-                             float, int, hipStream_t);
-hipError_t aca_cnn_trunk_rows(const uint8_t*, const uint16_t*, const float*, const uint16_t*, const float*,
-                              const uint16_t*, const float*, uint16_t*, uint16_t*, uint16_t*, int, float, uint8_t*,
-                              uint8_t*, uint64_t*, int, int, hipStream_t);
-}
+#include "launch_api.h"
 
 namespace {
 
@@ -161,9 +38,11 @@ void need(const Tensor& t, at::ScalarType dt, const char* name) {
 template <typename T>
 T* ptr(const Tensor& t) { return reinterpret_cast<T*>(t.data_ptr()); }
 
+bool has(const c10::optional<Tensor>& t) { return t.has_value() && t->defined(); }
+
 // optional per-workgroup phase timestamps [nblocks, 16] int64 (diagnostics; s_memrealtime ticks at 100 MHz)
 uint64_t* stamps_ptr(const c10::optional<Tensor>& st, int64_t nblocks) {
-  if (!(st.has_value() && st->defined())) return nullptr;
+  if (!has(st)) return nullptr;
   need(*st, at::kLong, "stamps");
   TORCH_CHECK(st->numel() >= nblocks * 16, "stamps: needs [nblocks, 16]");
   return ptr<uint64_t>(*st);
@@ -171,7 +50,9 @@ uint64_t* stamps_ptr(const c10::optional<Tensor>& st, int64_t nblocks) {
 
 
 template <typename T>
-T* optr(const c10::optional<Tensor>& t) { return (t.has_value() && t->defined()) ? ptr<T>(*t) : nullptr; }
+T* optr(const c10::optional<Tensor>& t) { return has(t) ? ptr<T>(*t) : nullptr; }
+
+bool aligned16(const Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; }
 
 // ---------------------------------------------------------------------------------------------- env banks
 void check_env(const Tensor& state, const Tensor& t, const Tensor& tg, const Tensor& ep_ret, const Tensor& ep_stats,
@@ -187,86 +68,224 @@ void check_env(const Tensor& state, const Tensor& t, const Tensor& tg, const Ten
   need(trunc, at::kByte, "truncated");
 }
 
-// optional terminal-observation output of the classic env kernels: same [N, k*D] stack shape as `out`
-float* final_out_ptr(const c10::optional<Tensor>& f, const Tensor& out) {
-  if (!(f.has_value() && f->defined())) return nullptr;
-  need(*f, at::kFloat, "final_out");
-  TORCH_CHECK(f->numel() == out.numel(), "final_out: must match the observation stack");
-  return ptr<float>(*f);
+// The validated operands of a vector-observation bank step: frame stacks prev / out [N, k * D] fp32; final_out
+// (optional terminal-observation output) has the same shape.
+aca::EnvIO env_io(const char* op, int64_t D, const Tensor& state, const Tensor& t, const Tensor& tg,
+                  const Tensor& ep_ret, const Tensor& ep_stats, const Tensor& ids, const Tensor& prev,
+                  const Tensor& out, const Tensor& reward, const Tensor& done, const Tensor& trunc, int64_t seed,
+                  int64_t max_steps, int64_t k, const c10::optional<Tensor>& final_out) {
+  check_env(state, t, tg, ep_ret, ep_stats, ids, reward, done, trunc);
+  need(prev, at::kFloat, "prev");
+  need(out, at::kFloat, "out");
+  const int64_t N = state.size(0);
+  TORCH_CHECK(prev.numel() == N * D * k && out.numel() == prev.numel(), op, ": bad stack shape");
+  aca::EnvIO io{};
+  io.state = ptr<float>(state);
+  io.t = ptr<int32_t>(t);
+  io.tg = ptr<int64_t>(tg);
+  io.ep_ret = ptr<float>(ep_ret);
+  io.ep_stats = ptr<float>(ep_stats);
+  io.env_ids = ptr<int64_t>(ids);
+  io.prev = ptr<float>(prev);
+  io.out = ptr<float>(out);
+  io.reward = ptr<float>(reward);
+  io.done = ptr<uint8_t>(done);
+  io.truncated = ptr<uint8_t>(trunc);
+  if (has(final_out)) {
+    need(*final_out, at::kFloat, "final_out");
+    TORCH_CHECK(final_out->numel() == out.numel(), "final_out: must match the observation stack");
+    io.final_out = ptr<float>(*final_out);
+  }
+  io.seed = (uint32_t)seed;
+  io.max_steps = (int)max_steps;
+  io.k = (int)k;
+  io.N = (int)N;
+  return io;
 }
 
 void env_step_cartpole(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids, Tensor actions,
                        Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc, int64_t seed,
                        int64_t max_steps, int64_t k, c10::optional<Tensor> final_out) {
-  check_env(state, t, tg, ep_ret, ep_stats, ids, reward, done, trunc);
+  const aca::EnvIO io = env_io("cartpole", 4, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed,
+                               max_steps, k, final_out);
   need(actions, at::kInt, "actions");
-  need(prev, at::kFloat, "prev");
-  need(out, at::kFloat, "out");
-  const int N = state.size(0);
-  TORCH_CHECK(prev.numel() == (int64_t)N * 4 * k && out.numel() == prev.numel(), "cartpole: bad stack shape");
-  check(aca_env_step_cartpole(ptr<float>(state), ptr<int32_t>(t), ptr<int64_t>(tg), ptr<float>(ep_ret),
-                              ptr<float>(ep_stats), ptr<int64_t>(ids), ptr<int32_t>(actions), ptr<float>(prev),
-                              ptr<float>(out), ptr<float>(reward), ptr<uint8_t>(done), ptr<uint8_t>(trunc),
-                              (uint32_t)seed, (int)max_steps, (int)k, N, final_out_ptr(final_out, out),
-                              cur_stream(state)),
-        "env_step_cartpole");
+  check(aca_env_step_cartpole(&io, ptr<int32_t>(actions), cur_stream(state)), "env_step_cartpole");
 }
 
 void env_step_pendulum(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids, Tensor actions,
                        Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc, int64_t seed,
                        int64_t max_steps, int64_t k, c10::optional<Tensor> final_out) {
-  check_env(state, t, tg, ep_ret, ep_stats, ids, reward, done, trunc);
+  const aca::EnvIO io = env_io("pendulum", 3, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed,
+                               max_steps, k, final_out);
   need(actions, at::kFloat, "actions");
-  need(prev, at::kFloat, "prev");
-  need(out, at::kFloat, "out");
-  const int N = state.size(0);
-  TORCH_CHECK(prev.numel() == (int64_t)N * 3 * k && out.numel() == prev.numel(), "pendulum: bad stack shape");
-  const int act_dim = actions.numel() / N;
-  check(aca_env_step_pendulum(ptr<float>(state), ptr<int32_t>(t), ptr<int64_t>(tg), ptr<float>(ep_ret),
-                              ptr<float>(ep_stats), ptr<int64_t>(ids), ptr<float>(actions), act_dim, ptr<float>(prev),
-                              ptr<float>(out), ptr<float>(reward), ptr<uint8_t>(done), ptr<uint8_t>(trunc),
-                              (uint32_t)seed, (int)max_steps, (int)k, N, final_out_ptr(final_out, out),
-                              cur_stream(state)),
-        "env_step_pendulum");
+  const int act_dim = actions.numel() / io.N;
+  check(aca_env_step_pendulum(&io, ptr<float>(actions), act_dim, cur_stream(state)), "env_step_pendulum");
 }
 
 void env_step_linear(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids, Tensor actions,
                      Tensor A, Tensor B, Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc,
                      int64_t seed, int64_t max_steps, int64_t k, c10::optional<Tensor> final_out) {
-  check_env(state, t, tg, ep_ret, ep_stats, ids, reward, done, trunc);
+  const aca::EnvIO io = env_io("linear", 17, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed,
+                               max_steps, k, final_out);
   need(actions, at::kFloat, "actions");
   need(A, at::kFloat, "A");
   need(B, at::kFloat, "B");
-  need(prev, at::kFloat, "prev");
-  need(out, at::kFloat, "out");
-  const int N = state.size(0);
-  TORCH_CHECK(state.size(1) == 17 && A.numel() == 17 * 17 && B.numel() == 17 * 6 && actions.numel() == N * 6,
+  TORCH_CHECK(state.size(1) == 17 && A.numel() == 17 * 17 && B.numel() == 17 * 6 && actions.numel() == io.N * 6,
               "linear env: bad shapes");
-  TORCH_CHECK(prev.numel() == (int64_t)N * 17 * k && out.numel() == prev.numel(), "linear: bad stack shape");
-  check(aca_env_step_linear(ptr<float>(state), ptr<int32_t>(t), ptr<int64_t>(tg), ptr<float>(ep_ret),
-                            ptr<float>(ep_stats), ptr<int64_t>(ids), ptr<float>(actions), ptr<float>(A),
-                            ptr<float>(B), ptr<float>(prev), ptr<float>(out), ptr<float>(reward),
-                            ptr<uint8_t>(done), ptr<uint8_t>(trunc), (uint32_t)seed, (int)max_steps, (int)k, N,
-                            final_out_ptr(final_out, out), cur_stream(state)),
+  check(aca_env_step_linear(&io, ptr<float>(actions), ptr<float>(A), ptr<float>(B), cur_stream(state)),
         "env_step_linear");
+}
+
+// The validated operands of a Pong-shaped bank step: state [N, 8], frame stacks [N, k, 84, 84] uint8. prev = nullptr
+// (the fused per-env step): one stack, read and written in place.
+aca::PongIO pong_io(const char* op, const Tensor& state, const Tensor& t, const Tensor& tg, const Tensor& ep_ret,
+                    const Tensor& ep_stats, const Tensor& ids, const Tensor* prev, const Tensor& out,
+                    const Tensor& reward, const Tensor& done, const Tensor& trunc, int64_t seed, int64_t max_steps,
+                    int64_t k) {
+  check_env(state, t, tg, ep_ret, ep_stats, ids, reward, done, trunc);
+  need(out, at::kByte, "out");
+  TORCH_CHECK(state.dim() == 2 && state.size(1) == 8, op, ": state must be [N, 8]");
+  TORCH_CHECK(out.numel() == state.size(0) * k * 84 * 84, op, ": bad stack shape, frame stacks are [N, k, 84, 84]");
+  aca::PongIO io{};
+  if (prev) {
+    need(*prev, at::kByte, "prev");
+    TORCH_CHECK(prev->numel() == out.numel(), op, ": bad stack shape, prev and out differ");
+    TORCH_CHECK(prev->data_ptr() != out.data_ptr(), op, ": prev and out must not alias");
+    io.prev = ptr<uint8_t>(*prev);
+  }
+  io.state = ptr<float>(state);
+  io.tsteps = ptr<int32_t>(t);
+  io.tglob = ptr<int64_t>(tg);
+  io.ep_ret = ptr<float>(ep_ret);
+  io.ep_stats = ptr<float>(ep_stats);
+  io.env_ids = ptr<int64_t>(ids);
+  io.out = ptr<uint8_t>(out);
+  io.reward = ptr<float>(reward);
+  io.done_out = ptr<uint8_t>(done);
+  io.trunc_out = ptr<uint8_t>(trunc);
+  io.seed = (uint32_t)seed;
+  io.max_steps = (int)max_steps;
+  io.k = (int)k;
+  return io;
+}
+
+// the other parity's env state of the fused steps: separate buffers of the same shape
+aca::PongNext pong_next(const char* op, const Tensor& state_n, const Tensor& t_n, const Tensor& tg_n,
+                        const Tensor& ep_ret_n, const Tensor& state, const Tensor& t, const Tensor& tg,
+                        const Tensor& ep_ret) {
+  need(state_n, at::kFloat, "next state");
+  need(t_n, at::kInt, "next t");
+  need(tg_n, at::kLong, "next tg");
+  need(ep_ret_n, at::kFloat, "next ep_ret");
+  TORCH_CHECK(state_n.sizes() == state.sizes() && t_n.numel() == t.numel() && tg_n.numel() == tg.numel() &&
+                  ep_ret_n.numel() == ep_ret.numel() && state_n.data_ptr() != state.data_ptr() &&
+                  t_n.data_ptr() != t.data_ptr() && tg_n.data_ptr() != tg.data_ptr() &&
+                  ep_ret_n.data_ptr() != ep_ret.data_ptr(),
+              op, ": the next-parity env state must be separate buffers of the same shape");
+  aca::PongNext nx{};
+  nx.state = ptr<float>(state_n);
+  nx.tsteps = ptr<int32_t>(t_n);
+  nx.tglob = ptr<int64_t>(tg_n);
+  nx.ep_ret = ptr<float>(ep_ret_n);
+  return nx;
+}
+
+// The validated policy / value head of a rollout step over N envs: h [N, 512], Wh [512, A1], bh [A1] (A1 = actions +
+// value, 3..max_A1), z [>= N, A1] and the per-env sampler outputs.
+aca::PolicyArgs policy_args(const char* op, int max_A1, const Tensor& h, const Tensor& Wh, const Tensor& bh,
+                            const Tensor& z, const Tensor& act, const Tensor& logp, const Tensor& ent,
+                            const Tensor& value, int64_t key_shift, int64_t pseed, int64_t N) {
+  for (const Tensor* x : {&h, &Wh}) need(*x, at::kBFloat16, "policy head bf16 operand (h, Wh)");
+  for (const Tensor* x : {&bh, &z, &logp, &ent, &value}) need(*x, at::kFloat, "policy head f32 operand");
+  need(act, at::kInt, "act");
+  const int64_t A1 = bh.numel();
+  TORCH_CHECK(A1 >= 3 && A1 <= max_A1, op, ": 2..", max_A1 - 1, " actions");
+  TORCH_CHECK(h.numel() == N * 512 && Wh.numel() == 512 * A1 && z.numel() >= N * A1 && act.numel() >= N &&
+                  value.numel() >= N, op, ": bad head shapes (hidden size 512)");
+  TORCH_CHECK(aligned16(h) && aligned16(Wh), op, ": h and Wh must be 16-byte aligned buffers");
+  aca::PolicyArgs p{};
+  p.h = ptr<uint16_t>(h);
+  p.Wh = ptr<uint16_t>(Wh);
+  p.bh = ptr<float>(bh);
+  p.A = (int)A1 - 1;
+  p.z = ptr<float>(z);
+  p.act = ptr<int32_t>(act);
+  p.logp = ptr<float>(logp);
+  p.ent = ptr<float>(ent);
+  p.value = ptr<float>(value);
+  p.key_shift = (int)key_shift;
+  p.pseed = (uint32_t)pseed;
+  return p;
+}
+
+// The rollout's last fc product as split-K partial planes: hpart holds 32 equal planes of [>= N, 512] fp32
+// (engine.py FC_PLANES), `planes` of them written; bfc [512] the fc bias.
+aca::FcParts fc_parts(const char* op, const Tensor& hpart, int64_t planes, const Tensor& bfc, int64_t N) {
+  need(hpart, at::kFloat, "hpart");
+  need(bfc, at::kFloat, "bfc");
+  TORCH_CHECK(planes >= 1 && planes <= 32 && hpart.numel() % 32 == 0 && bfc.numel() == 512,
+              op, ": hpart must hold 32 planes (1..32 fc planes written), bfc [512]");
+  aca::FcParts fc{};
+  fc.hpart = ptr<float>(hpart);
+  fc.S = (int)planes;
+  fc.plane_stride = hpart.numel() / 32;
+  fc.bfc = ptr<float>(bfc);
+  TORCH_CHECK(fc.plane_stride >= N * 512, op, ": hpart planes too small, need [N, 512]");
+  return fc;
+}
+
+// optional form: no hpart -> all null (the kernel reads finished values instead)
+aca::FcParts fc_parts(const char* op, const c10::optional<Tensor>& hpart, int64_t planes,
+                      const c10::optional<Tensor>& bfc, int64_t N) {
+  if (!has(hpart)) return aca::FcParts{};
+  TORCH_CHECK(has(bfc), op, ": hpart needs bfc");
+  return fc_parts(op, *hpart, planes, *bfc, N);
+}
+
+// The validated conv trunk of B observations (cnn_args.h TrunkArgs; shapes fixed by the kernels). exact: the
+// activation buffers hold exactly B samples. shift_out (optional): a distinct, aligned buffer shaped like `frames`.
+aca::TrunkArgs trunk_args(const char* op, const Tensor& W1, const Tensor& b1, const Tensor& W2, const Tensor& b2,
+                          const Tensor& W3, const Tensor& b3, const Tensor& y1, const Tensor& y2, const Tensor& y3,
+                          double scale, const c10::optional<Tensor>& shift_out, const Tensor& frames, int64_t B,
+                          bool exact) {
+  for (const Tensor* x : {&W1, &W2, &W3, &y1, &y2, &y3}) need(*x, at::kBFloat16, "trunk bf16 operand");
+  for (const Tensor* x : {&b1, &b2, &b3}) need(*x, at::kFloat, "trunk bias");
+  TORCH_CHECK(W1.numel() == 32 * 256 && W2.numel() == 64 * 512 && W3.numel() == 64 * 576 && b1.numel() == 32 &&
+                  b2.numel() == 64 && b3.numel() == 64, op, ": weights / biases must be Nature-CNN conv1..3");
+  const int64_t n1 = B * 400 * 32, n2 = B * 81 * 64, n3 = B * 49 * 64;
+  TORCH_CHECK(exact ? (y1.numel() == n1 && y2.numel() == n2 && y3.numel() == n3)
+                    : (y1.numel() >= n1 && y2.numel() >= n2 && y3.numel() >= n3),
+              op, ": trunk shapes (activation buffers y1 [B*400, 32], y2 [B*81, 64], y3 [B*49, 64])");
+  for (const Tensor* x : {&W1, &W2, &W3, &y1, &y2, &y3})
+    TORCH_CHECK(aligned16(*x), op, ": 16-byte aligned buffers (trunk operands)");
+  aca::TrunkArgs tr{};
+  tr.W1 = ptr<uint16_t>(W1);
+  tr.b1 = ptr<float>(b1);
+  tr.W2 = ptr<uint16_t>(W2);
+  tr.b2 = ptr<float>(b2);
+  tr.W3 = ptr<uint16_t>(W3);
+  tr.b3 = ptr<float>(b3);
+  tr.y1 = ptr<uint16_t>(y1);
+  tr.y2 = ptr<uint16_t>(y2);
+  tr.y3 = ptr<uint16_t>(y3);
+  tr.scale = (float)scale;
+  if (has(shift_out)) {
+    need(*shift_out, at::kByte, "shift_out");
+    TORCH_CHECK(shift_out->numel() == frames.numel() && aligned16(*shift_out) &&
+                    shift_out->data_ptr() != frames.data_ptr(),
+                op, ": shift_out must be a distinct, aligned [B, 4, 84, 84] uint8 buffer");
+    tr.shift_out = ptr<uint8_t>(*shift_out);
+  }
+  return tr;
 }
 
 void env_step_pong(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids, Tensor actions,
                    Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc, int64_t seed, int64_t max_steps,
                    int64_t k) {
-  check_env(state, t, tg, ep_ret, ep_stats, ids, reward, done, trunc);
+  const aca::PongIO io = pong_io("pong", state, t, tg, ep_ret, ep_stats, ids, &prev, out, reward, done, trunc, seed,
+                                 max_steps, k);
   need(actions, at::kInt, "actions");
-  need(prev, at::kByte, "prev");
-  need(out, at::kByte, "out");
-  const int N = state.size(0);
-  TORCH_CHECK(state.size(1) == 8, "pong: state must be [N, 8]");
-  TORCH_CHECK(prev.numel() == (int64_t)N * k * 84 * 84 && out.numel() == prev.numel(), "pong: bad stack shape");
-  TORCH_CHECK(prev.data_ptr() != out.data_ptr(), "pong: prev and out must not alias");
-  check(aca_env_step_pong(ptr<float>(state), ptr<int32_t>(t), ptr<int64_t>(tg), ptr<float>(ep_ret),
-                          ptr<float>(ep_stats), ptr<int64_t>(ids), ptr<int32_t>(actions), ptr<uint8_t>(prev),
-                          ptr<uint8_t>(out), ptr<float>(reward), ptr<uint8_t>(done), ptr<uint8_t>(trunc),
-                          (uint32_t)seed, (int)max_steps, (int)k, N, cur_stream(state)),
-        "env_step_pong");
+  check(aca_env_step_pong(&io, ptr<int32_t>(actions), (int)state.size(0), cur_stream(state)), "env_step_pong");
 }
 
 // fused rollout step: policy/value head + sampling + env step (native engine, Pong/Breakout-shaped banks)
@@ -276,50 +295,14 @@ void env_policy_step_pong(Tensor h, Tensor Wh, Tensor bh, Tensor z, Tensor act, 
                           Tensor done, Tensor trunc, int64_t seed, int64_t max_steps, int64_t k, bool pre_shifted,
                           c10::optional<Tensor> hpart, int64_t planes, c10::optional<Tensor> bfc,
                           c10::optional<Tensor> stamps) {
-  check_env(state, t, tg, ep_ret, ep_stats, ids, reward, done, trunc);
-  need(h, at::kBFloat16, "h");
-  need(Wh, at::kBFloat16, "Wh");
-  need(bh, at::kFloat, "bh");
-  need(z, at::kFloat, "z");
-  need(act, at::kInt, "act");
-  need(logp, at::kFloat, "logp");
-  need(ent, at::kFloat, "ent");
-  need(value, at::kFloat, "value");
-  need(prev, at::kByte, "prev");
-  need(out, at::kByte, "out");
+  const char* op = "env_policy_step_pong";
+  const aca::PongIO io = pong_io(op, state, t, tg, ep_ret, ep_stats, ids, &prev, out, reward, done, trunc, seed,
+                                 max_steps, k);
   const int N = state.size(0);
-  const int A1 = bh.numel(), A = A1 - 1;
-  const int hdim = h.numel() / N;
-  TORCH_CHECK(state.size(1) == 8 && h.numel() == (int64_t)N * hdim && Wh.numel() == (int64_t)hdim * A1 &&
-                  z.numel() >= (int64_t)N * A1 && act.numel() >= N && value.numel() >= N,
-              "env_policy_step_pong: bad shapes");
-  TORCH_CHECK(A1 >= 3 && A1 <= 20 && hdim == 512 && reinterpret_cast<uintptr_t>(Wh.data_ptr()) % 16 == 0 &&
-                  reinterpret_cast<uintptr_t>(h.data_ptr()) % 16 == 0,
-              "env_policy_step_pong: 2..19 actions, hidden size 512, h and Wh 16-byte aligned");
-  TORCH_CHECK(prev.numel() == (int64_t)N * k * 84 * 84 && out.numel() == prev.numel(), "pong: bad stack shape");
-  TORCH_CHECK(prev.data_ptr() != out.data_ptr(), "pong: prev and out must not alias");
-  const float* hp = nullptr;
-  const float* bf = nullptr;
-  int64_t pstride = 0;
-  if (hpart.has_value() && hpart->defined()) {
-    need(*hpart, at::kFloat, "hpart");
-    TORCH_CHECK(bfc.has_value() && bfc->defined() && bfc->numel() == hdim, "env_policy_step_pong: hpart needs bfc");
-    need(*bfc, at::kFloat, "bfc");
-    TORCH_CHECK(planes >= 1 && planes <= 32 && hpart->numel() % 32 == 0, "env_policy_step_pong: 1..32 planes");
-    pstride = hpart->numel() / 32;   // buffer holds 32 planes of equal size (engine.py FC_PLANES)
-    TORCH_CHECK(pstride >= (int64_t)N * hdim, "env_policy_step_pong: hpart planes too small");
-    hp = ptr<float>(*hpart);
-    bf = ptr<float>(*bfc);
-  }
-  check(aca_env_policy_step_pong(ptr<uint16_t>(h), hp, (int)planes, pstride, bf, hdim, ptr<uint16_t>(Wh),
-                                 ptr<float>(bh), A, ptr<float>(z),
-                                 ptr<int32_t>(act), ptr<float>(logp), ptr<float>(ent), ptr<float>(value),
-                                 (int)key_shift, (uint32_t)pseed, ptr<float>(state), ptr<int32_t>(t),
-                                 ptr<int64_t>(tg), ptr<float>(ep_ret), ptr<float>(ep_stats), ptr<int64_t>(ids),
-                                 ptr<uint8_t>(prev), ptr<uint8_t>(out), ptr<float>(reward), ptr<uint8_t>(done),
-                                 ptr<uint8_t>(trunc), (uint32_t)seed, (int)max_steps, (int)k, N, pre_shifted ? 1 : 0,
-                                 stamps_ptr(stamps, N), cur_stream(state)),
-        "env_policy_step_pong");
+  const aca::PolicyArgs pol = policy_args(op, 20, h, Wh, bh, z, act, logp, ent, value, key_shift, pseed, N);
+  const aca::FcParts fc = fc_parts(op, hpart, planes, bfc, N);
+  check(aca_env_policy_step_pong(&io, &fc, &pol, 512, N, pre_shifted ? 1 : 0, stamps_ptr(stamps, N),
+                                 cur_stream(state)), op);
 }
 
 // Rollout step t of the Pong bank fused with the row-split trunk of the observation it produces (cnn_fused.hip
@@ -334,52 +317,17 @@ void pong_fused_step(Tensor h, Tensor Wh, Tensor bh, Tensor z, Tensor act, Tenso
                      Tensor b2, Tensor W3, Tensor b3, Tensor y1, Tensor y2, Tensor y3, double scale,
                      c10::optional<Tensor> shift_out, c10::optional<Tensor> stamps, bool frag) {
   // frag: W2 / W3 are the fragment-ordered copies (ops/optim.py frag_order); W1 row-major
-  check_env(state, t, tg, ep_ret, ep_stats, ids, reward, done, trunc);
-  check_env(state_n, t_n, tg_n, ep_ret_n, ep_stats, ids, reward, done, trunc);
-  for (auto* x : {&h, &Wh, &W1, &W2, &W3, &y1, &y2, &y3}) need(*x, at::kBFloat16, "pong_fused_step bf16");
-  for (auto* x : {&bh, &z, &logp, &ent, &value, &hpart, &bfc, &b1, &b2, &b3}) need(*x, at::kFloat, "pong_fused_step f32");
-  need(act, at::kInt, "act");
-  need(prev, at::kByte, "prev");
-  need(out, at::kByte, "out");
+  const char* op = "pong_fused_step";
+  const aca::PongIO io = pong_io(op, state, t, tg, ep_ret, ep_stats, ids, &prev, out, reward, done, trunc, seed,
+                                 max_steps, 4);
+  const aca::PongNext nx = pong_next(op, state_n, t_n, tg_n, ep_ret_n, state, t, tg, ep_ret);
   const int N = state.size(0);
-  const int A1 = bh.numel(), A = A1 - 1;
-  TORCH_CHECK(A1 >= 3 && A1 <= 7, "pong_fused_step: 2..6 actions");
-  TORCH_CHECK(state.size(1) == 8 && h.numel() == (int64_t)N * 512 && Wh.numel() == 512 * A1 &&
-                  z.numel() >= (int64_t)N * A1 && act.numel() >= N && value.numel() >= N,
-              "pong_fused_step: bad head shapes");
-  TORCH_CHECK(prev.numel() == (int64_t)N * 4 * 84 * 84 && out.numel() == prev.numel() &&
-                  prev.data_ptr() != out.data_ptr(), "pong_fused_step: frame stacks [N, 4, 84, 84], not aliased");
-  TORCH_CHECK(state.data_ptr() != state_n.data_ptr() && t.data_ptr() != t_n.data_ptr() &&
-                  tg.data_ptr() != tg_n.data_ptr() && ep_ret.data_ptr() != ep_ret_n.data_ptr(),
-              "pong_fused_step: the next-parity env state must be separate buffers");
-  TORCH_CHECK(W1.numel() == 32 * 256 && W2.numel() == 64 * 512 && W3.numel() == 64 * 576 && b1.numel() == 32 &&
-                  b2.numel() == 64 && b3.numel() == 64 && y1.numel() == (int64_t)N * 400 * 32 &&
-                  y2.numel() == (int64_t)N * 81 * 64 && y3.numel() == (int64_t)N * 49 * 64,
-              "pong_fused_step: trunk shapes");
-  for (const Tensor* x : {&prev, &out, &W1, &W2, &W3, &y1, &y2, &y3, &h, &Wh})
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(x->data_ptr()) % 16 == 0, "pong_fused_step: 16-byte aligned buffers");
-  TORCH_CHECK(planes >= 1 && planes <= 32 && hpart.numel() % 32 == 0 && bfc.numel() == 512,
-              "pong_fused_step: 1..32 fc planes");
-  const int64_t pstride = hpart.numel() / 32;
-  TORCH_CHECK(pstride >= (int64_t)N * 512, "pong_fused_step: hpart planes too small");
-  uint8_t* so = nullptr;
-  if (shift_out.has_value() && shift_out->defined()) {
-    need(*shift_out, at::kByte, "shift_out");
-    TORCH_CHECK(shift_out->numel() == prev.numel() && reinterpret_cast<uintptr_t>(shift_out->data_ptr()) % 16 == 0 &&
-                    shift_out->data_ptr() != out.data_ptr(), "pong_fused_step: shift_out shape / aliasing");
-    so = shift_out->data_ptr<uint8_t>();
-  }
-  check(aca_pong_fused_step(ptr<uint16_t>(h), ptr<float>(hpart), (int)planes, pstride, ptr<float>(bfc),
-                            ptr<uint16_t>(Wh), ptr<float>(bh), A, ptr<float>(z), ptr<int32_t>(act), ptr<float>(logp),
-                            ptr<float>(ent), ptr<float>(value), (int)key_shift, (uint32_t)pseed, ptr<float>(state),
-                            ptr<int32_t>(t), ptr<int64_t>(tg), ptr<float>(ep_ret), ptr<float>(state_n),
-                            ptr<int32_t>(t_n), ptr<int64_t>(tg_n), ptr<float>(ep_ret_n), ptr<float>(ep_stats),
-                            ptr<int64_t>(ids), ptr<uint8_t>(prev), ptr<uint8_t>(out), ptr<float>(reward),
-                            ptr<uint8_t>(done), ptr<uint8_t>(trunc), (uint32_t)seed, (int)max_steps,
-                            ptr<uint16_t>(W1), ptr<float>(b1), ptr<uint16_t>(W2), ptr<float>(b2), ptr<uint16_t>(W3),
-                            ptr<float>(b3), ptr<uint16_t>(y1), ptr<uint16_t>(y2), ptr<uint16_t>(y3), (float)scale,
-                            so, stamps_ptr(stamps, N * 7), frag ? 1 : 0, N, cur_stream(state)),
-        "pong_fused_step");
+  const aca::PolicyArgs pol = policy_args(op, 7, h, Wh, bh, z, act, logp, ent, value, key_shift, pseed, N);
+  const aca::FcParts fc = fc_parts(op, hpart, planes, bfc, N);
+  const aca::TrunkArgs tr = trunk_args(op, W1, b1, W2, b2, W3, b3, y1, y2, y3, scale, shift_out, out, N, true);
+  TORCH_CHECK(aligned16(prev) && aligned16(out), op, ": 16-byte aligned buffers (frame stacks)");
+  check(aca_pong_fused_step(&io, &nx, &fc, &pol, &tr, stamps_ptr(stamps, N * 7), frag ? 1 : 0, N, cur_stream(state)),
+        op);
 }
 
 // Per-env fused rollout step (cnn_fused.hip pong_fused_env_step_kernel): policy/env step t of env e (fc planes of
@@ -395,58 +343,23 @@ void pong_fused_env_step(Tensor h, Tensor Wh, Tensor bh, Tensor z, Tensor act, T
                          double scale, c10::optional<Tensor> shift_out, c10::optional<std::vector<Tensor>> next_state,
                          c10::optional<Tensor> stamps, bool frag) {
   // frag: W2 / W3 are the fragment-ordered copies (ops/optim.py frag_order); W1 row-major
-  check_env(state, t, tg, ep_ret, ep_stats, ids, reward, done, trunc);
-  float* sn = nullptr; int32_t* tn = nullptr; int64_t* tgn = nullptr; float* ern = nullptr;
+  const char* op = "pong_fused_env_step";
+  const aca::PongIO io = pong_io(op, state, t, tg, ep_ret, ep_stats, ids, nullptr, out, reward, done, trunc, seed,
+                                 max_steps, 4);
+  aca::PongNext nx{};
   if (next_state.has_value()) {
     const auto& v = *next_state;
-    TORCH_CHECK(v.size() == 4, "pong_fused_env_step: next_state = [state, t, tg, ep_ret]");
-    check_env(v[0], v[1], v[2], v[3], ep_stats, ids, reward, done, trunc);
-    TORCH_CHECK(v[0].sizes() == state.sizes() && v[0].data_ptr() != state.data_ptr() &&
-                    v[1].data_ptr() != t.data_ptr() && v[2].data_ptr() != tg.data_ptr() &&
-                    v[3].data_ptr() != ep_ret.data_ptr(),
-                "pong_fused_env_step: the next-parity env state must be separate buffers of the same shape");
-    sn = ptr<float>(v[0]); tn = ptr<int32_t>(v[1]); tgn = ptr<int64_t>(v[2]); ern = ptr<float>(v[3]);
+    TORCH_CHECK(v.size() == 4, op, ": next_state = [state, t, tg, ep_ret]");
+    nx = pong_next(op, v[0], v[1], v[2], v[3], state, t, tg, ep_ret);
   }
-  for (auto* x : {&h, &Wh, &W1, &W2, &W3, &y1, &y2, &y3}) need(*x, at::kBFloat16, "pong_fused_env_step bf16");
-  for (auto* x : {&bh, &z, &logp, &ent, &value, &hpart, &bfc, &b1, &b2, &b3})
-    need(*x, at::kFloat, "pong_fused_env_step f32");
-  need(act, at::kInt, "act");
-  need(out, at::kByte, "out");
   const int N = state.size(0);
-  const int A1 = bh.numel();
-  TORCH_CHECK(A1 >= 3 && A1 <= 7, "pong_fused_env_step: 2..6 actions");
-  TORCH_CHECK(state.size(1) == 8 && h.numel() == (int64_t)N * 512 && Wh.numel() == 512 * A1 &&
-                  z.numel() >= (int64_t)N * A1 && act.numel() >= N && value.numel() >= N,
-              "pong_fused_env_step: bad head shapes");
-  TORCH_CHECK(out.numel() == (int64_t)N * 4 * 84 * 84, "pong_fused_env_step: frame stack [N, 4, 84, 84]");
-  TORCH_CHECK(W1.numel() == 32 * 256 && W2.numel() == 64 * 512 && W3.numel() == 64 * 576 && b1.numel() == 32 &&
-                  b2.numel() == 64 && b3.numel() == 64 && y1.numel() == (int64_t)N * 400 * 32 &&
-                  y2.numel() == (int64_t)N * 81 * 64 && y3.numel() == (int64_t)N * 49 * 64,
-              "pong_fused_env_step: trunk shapes");
-  for (const Tensor* x : {&out, &W1, &W2, &W3, &y1, &y2, &y3, &h, &Wh, &hpart, &bfc})
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(x->data_ptr()) % 16 == 0, "pong_fused_env_step: 16-byte aligned buffers");
-  TORCH_CHECK(planes >= 1 && planes <= 32 && hpart.numel() % 32 == 0 && bfc.numel() == 512,
-              "pong_fused_env_step: 1..32 fc planes");
-  const int64_t pstride = hpart.numel() / 32;
-  TORCH_CHECK(pstride >= (int64_t)N * 512, "pong_fused_env_step: hpart planes too small");
-  uint8_t* so = nullptr;
-  if (shift_out.has_value() && shift_out->defined()) {
-    need(*shift_out, at::kByte, "shift_out");
-    TORCH_CHECK(shift_out->numel() == out.numel() && reinterpret_cast<uintptr_t>(shift_out->data_ptr()) % 16 == 0 &&
-                    shift_out->data_ptr() != out.data_ptr(), "pong_fused_env_step: shift_out shape / aliasing");
-    so = shift_out->data_ptr<uint8_t>();
-  }
-  check(aca_pong_fused_env_step(ptr<uint16_t>(h), ptr<float>(hpart), (int)planes, pstride, ptr<float>(bfc),
-                                ptr<uint16_t>(Wh), ptr<float>(bh), A1 - 1, ptr<float>(z), ptr<int32_t>(act),
-                                ptr<float>(logp), ptr<float>(ent), ptr<float>(value), (int)key_shift, (uint32_t)pseed,
-                                ptr<float>(state), ptr<int32_t>(t), ptr<int64_t>(tg), ptr<float>(ep_ret),
-                                ptr<float>(ep_stats), ptr<int64_t>(ids), ptr<uint8_t>(out), ptr<float>(reward),
-                                ptr<uint8_t>(done), ptr<uint8_t>(trunc), (uint32_t)seed, (int)max_steps,
-                                ptr<uint16_t>(W1), ptr<float>(b1), ptr<uint16_t>(W2), ptr<float>(b2),
-                                ptr<uint16_t>(W3), ptr<float>(b3), ptr<uint16_t>(y1), ptr<uint16_t>(y2),
-                                ptr<uint16_t>(y3), (float)scale, so, sn, tn, tgn, ern, stamps_ptr(stamps, sn ? 2 * N : N),
-                                frag ? 1 : 0, N, cur_stream(state)),
-        "pong_fused_env_step");
+  const aca::PolicyArgs pol = policy_args(op, 7, h, Wh, bh, z, act, logp, ent, value, key_shift, pseed, N);
+  const aca::FcParts fc = fc_parts(op, hpart, planes, bfc, N);
+  const aca::TrunkArgs tr = trunk_args(op, W1, b1, W2, b2, W3, b3, y1, y2, y3, scale, shift_out, out, N, true);
+  TORCH_CHECK(aligned16(out) && aligned16(hpart) && aligned16(bfc), op,
+              ": 16-byte aligned buffers (frame stack, hpart, bfc)");
+  check(aca_pong_fused_env_step(&io, &nx, &fc, &pol, &tr, stamps_ptr(stamps, nx.state ? 2 * N : N), frag ? 1 : 0, N,
+                                cur_stream(state)), op);
 }
 
 // learner fc backward at B <= 256 rows (fc_bwd.hip): dy3 = (dh Wfc^T) * (y3 > 0) bf16, dW = y3^T dh fp32 (stored)
@@ -463,15 +376,20 @@ void fc_bwd(Tensor dh, Tensor W, Tensor y3, Tensor dy3, Tensor dW, c10::optional
     TORCH_CHECK(x->is_contiguous() && reinterpret_cast<uintptr_t>(x->data_ptr()) % 16 == 0,
                 "fc_bwd: contiguous 16-byte aligned buffers");
   const int64_t nwg = 392 + ((B + 31) / 32) * 49;
-  float* sqp = nullptr;
-  if (sq.has_value() && sq->defined()) {
+  aca::FcBwdArgs a{};
+  a.dh = ptr<uint16_t>(dh);
+  a.W = ptr<uint16_t>(W);
+  a.y3 = ptr<uint16_t>(y3);
+  a.dy3 = ptr<uint16_t>(dy3);
+  a.dW = ptr<float>(dW);
+  a.B = (int)B;
+  a.stamps = stamps_ptr(stamps, nwg / 4 + 1);
+  if (has(sq)) {
     need(*sq, at::kFloat, "fc_bwd sq");
     TORCH_CHECK(sq->numel() >= 392 * 4, "fc_bwd: sq needs 1568 floats");
-    sqp = ptr<float>(*sq);
+    a.sq = ptr<float>(*sq);
   }
-  check(aca_fc_bwd(ptr<uint16_t>(dh), ptr<uint16_t>(W), ptr<uint16_t>(y3), ptr<uint16_t>(dy3), ptr<float>(dW), (int)B,
-                   sqp, stamps_ptr(stamps, nwg / 4 + 1), cur_stream(dh)),
-        "fc_bwd");
+  check(aca_fc_bwd(&a, cur_stream(dh)), "fc_bwd");
 }
 
 // rollout fc product as split-K partial planes on the fragment-ordered Wfc copy (fc_rollout.hip); hpart holds 32
@@ -485,35 +403,37 @@ int64_t fc_rollout(Tensor X, Tensor Wf, Tensor hpart, int64_t variant, c10::opti
               "fc_rollout: X must be [M <= 128, 3136] row-major");
   TORCH_CHECK(Wf.numel() == 3136 * 512 && Wf.is_contiguous(), "fc_rollout: Wf must be the [3136 x 512] fragment copy");
   TORCH_CHECK(hpart.numel() % 32 == 0 && hpart.numel() / 32 >= X.size(0) * 512, "fc_rollout: hpart must hold 32 planes");
+  aca::FcRolloutArgs a{};
+  a.X = ptr<uint16_t>(X);
+  a.ldx = X.stride(0);
+  a.M = (int)X.size(0);
+  a.Wf = ptr<uint16_t>(Wf);
+  a.K = 3136;
+  a.N = 512;
+  a.P = ptr<float>(hpart);
+  a.pstride = hpart.numel() / 32;
+  a.stamps = reinterpret_cast<unsigned long long*>(stamps_ptr(stamps, 1));
   int S = 0;
-  check(aca_fc_rollout(ptr<uint16_t>(X), X.stride(0), (int)X.size(0), ptr<uint16_t>(Wf), 3136, 512, ptr<float>(hpart),
-                       hpart.numel() / 32, (int)(variant & 15), 32, &S,
-                       reinterpret_cast<unsigned long long*>(stamps_ptr(stamps, 1)), variant >= 16 ? 1 : 0,
-                       cur_stream(X)),
-        "fc_rollout");
+  check(aca_fc_rollout(&a, (int)(variant & 15), 32, &S, variant >= 16 ? 1 : 0, cur_stream(X)), "fc_rollout");
   return S;
 }
 
 // bootstrap value from the fc partial planes (cnn_fused.hip); hpart holds 32 equal planes of [N, 512]
 void fc_value(Tensor hpart, int64_t planes, Tensor bfc, Tensor Wh, Tensor bh, Tensor out, c10::optional<Tensor> h_out) {
-  need(hpart, at::kFloat, "hpart");
-  need(bfc, at::kFloat, "bfc");
   need(Wh, at::kBFloat16, "Wh");
   need(bh, at::kFloat, "bh");
   need(out, at::kFloat, "out");
   const int N = out.numel(), A1 = bh.numel();
-  const int64_t pstride = hpart.numel() / 32;
-  TORCH_CHECK(hpart.numel() % 32 == 0 && pstride >= (int64_t)N * 512 && planes >= 1 && planes <= 32,
-              "fc_value: hpart must hold 32 planes of [N, 512]");
-  TORCH_CHECK(bfc.numel() == 512 && Wh.numel() == 512 * A1, "fc_value: bad head shapes");
+  const aca::FcParts fc = fc_parts("fc_value", hpart, planes, bfc, N);
+  TORCH_CHECK(Wh.numel() == 512 * A1, "fc_value: bad head shapes");
   uint16_t* ho = nullptr;
-  if (h_out.has_value() && h_out->defined()) {
+  if (has(h_out)) {
     need(*h_out, at::kBFloat16, "h_out");
     TORCH_CHECK(h_out->numel() >= (int64_t)N * 512, "fc_value: h_out too small");
     ho = ptr<uint16_t>(*h_out);
   }
-  check(aca_fc_value(ptr<float>(hpart), (int)planes, pstride, ptr<float>(bfc), ptr<uint16_t>(Wh), A1, ptr<float>(bh),
-                     ptr<float>(out), ho, N, cur_stream(out)),
+  check(aca_fc_value(fc.hpart, fc.S, fc.plane_stride, fc.bfc, ptr<uint16_t>(Wh), A1, ptr<float>(bh), ptr<float>(out),
+                     ho, N, cur_stream(out)),
         "fc_value");
 }
 
@@ -557,7 +477,7 @@ void categorical_sample_env(Tensor logits, Tensor tg, Tensor env_ids, int64_t ke
   TORCH_CHECK(tg.numel() >= B && env_ids.numel() >= B && act.numel() >= B && logp.numel() >= B && ent.numel() >= B,
               "bad sizes");
   float* vo = nullptr;
-  if (vout.has_value() && vout->defined()) {
+  if (has(vout)) {
     need(*vout, at::kFloat, "vout");
     TORCH_CHECK(vout->numel() >= B && logits.stride(0) > A, "vout needs a value column after the logits");
     vo = ptr<float>(*vout);
@@ -616,14 +536,14 @@ void normalize(Tensor a, Tensor out, double eps) {
   check(aca_normalize(ptr<float>(a), ptr<float>(out), a.numel(), (float)eps, cur_stream(a)), "normalize");
 }
 
-// ev(x, y, out[, part, ticket]): with a workspace (part fp64 [>= ev_blocks(n) * 8], ticket int32 zeroed once) the
+// ev(x, y, out[, part, ticket]): with a workspace (part fp64 [>= ev_multi_blocks(n) * 8], ticket int32 zeroed once) the
 // many-workgroup form runs; without, the one-workgroup kernel.
 void ev(Tensor x, Tensor y, Tensor out, c10::optional<Tensor> part, c10::optional<Tensor> ticket) {
   need(x, at::kFloat, "x");
   need(y, at::kFloat, "y");
   TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat && out.numel() >= 1, "ev: out must be fp32");
   TORCH_CHECK(x.numel() == y.numel(), "ev: size mismatch");
-  if (part.has_value() && part->defined()) {
+  if (has(part)) {
     need(*part, at::kDouble, "part");
     TORCH_CHECK(ticket.has_value() && ticket->is_cuda() && ticket->scalar_type() == at::kInt, "ev: ticket int32");
     TORCH_CHECK(part->numel() >= aca_ev_multi_blocks(x.numel()) * 8, "ev: part too small");
@@ -634,8 +554,6 @@ void ev(Tensor x, Tensor y, Tensor out, c10::optional<Tensor> part, c10::optiona
   }
   check(aca_ev(ptr<float>(x), ptr<float>(y), ptr<float>(out), x.numel(), cur_stream(x)), "ev");
 }
-
-int64_t ev_blocks(int64_t n) { return aca_ev_multi_blocks((int)n); }
 
 std::vector<int64_t> returns_scan_geometry(int64_t T, int64_t N) {
   int E, CH, K, blocks;
@@ -656,23 +574,34 @@ void returns_scan(Tensor r, Tensor v, Tensor d, Tensor ret, Tensor adv, int64_t 
   need(mom, at::kDouble, "mom");
   TORCH_CHECK(part.numel() >= (int64_t)blocks * 8 && mom.numel() >= 8, "returns_scan: workspace too small");
   TORCH_CHECK(ticket.is_cuda() && ticket.scalar_type() == at::kInt, "returns_scan: ticket int32");
-  double* gzp = nullptr;
+  aca::RetScanArgs a{};
+  a.r = ptr<float>(r);
+  a.v = ptr<float>(v);
+  a.d = ptr<uint8_t>(d);
+  a.ret = ptr<float>(ret);
+  a.adv = ptr<float>(adv);
   if (mode == 1 && L < T) {
-    TORCH_CHECK(gz.has_value() && gz->defined(), "returns_scan: truncated n-step needs a gz workspace");
+    TORCH_CHECK(has(gz), "returns_scan: truncated n-step needs a gz workspace");
     need(*gz, at::kDouble, "gz");
     TORCH_CHECK(gz->numel() >= (int64_t)T * N, "returns_scan: gz too small");
-    gzp = ptr<double>(*gz);
+    a.gz = ptr<double>(*gz);
   }
-  float* evp = nullptr;
-  if (ev_out.has_value() && ev_out->defined()) {
+  a.part = ptr<double>(part);
+  a.ticket = reinterpret_cast<unsigned int*>(ticket.data_ptr<int>());
+  a.mom = ptr<double>(mom);
+  if (has(ev_out)) {
     need(*ev_out, at::kFloat, "ev_out");
-    evp = ptr<float>(*ev_out);
+    a.ev_out = ptr<float>(*ev_out);
   }
-  check(aca_returns_scan(ptr<float>(r), ptr<float>(v), ptr<uint8_t>(d), ptr<float>(ret), ptr<float>(adv), gzp,
-                         ptr<double>(part), reinterpret_cast<unsigned int*>(ticket.data_ptr<int>()), ptr<double>(mom),
-                         evp, T, N, (int)mode, (int)L, norm ? 1 : 0, (float)gamma, (float)lam, (float)eps,
-                         cur_stream(r)),
-        "returns_scan");
+  a.T = T;
+  a.N = N;
+  a.mode = (int)mode;
+  a.L = (int)L;
+  a.norm = norm ? 1 : 0;
+  a.gamma = (float)gamma;
+  a.lam = (float)lam;
+  a.eps = (float)eps;
+  check(aca_returns_scan(&a, cur_stream(r)), "returns_scan");
 }
 
 // conv1 weight gradient as P partial planes [P][32][256] (conv_wgrad.hip): obs uint8 [B, 4, 84, 84], dy1 bf16
@@ -687,7 +616,7 @@ void conv1_wgrad(Tensor obs, Tensor dy1, Tensor planes, int64_t P, double scale,
   TORCH_CHECK(rows >= 1 && obs.numel() == rows * 4 * 84 * 84, "conv1_wgrad: obs [n, 4, 84, 84]");
   const int64_t* idx = nullptr;
   int64_t B = rows;
-  if (obs_idx.has_value() && obs_idx->defined()) {
+  if (has(obs_idx)) {
     need(*obs_idx, at::kLong, "obs_idx");
     B = obs_idx->numel();
     idx = obs_idx->data_ptr<int64_t>();
@@ -728,50 +657,61 @@ void mb_gather(Tensor obs, Tensor act, Tensor logp, Tensor adv, Tensor ret, Tens
                Tensor o_act, Tensor o_logp, Tensor o_adv, Tensor o_ret, Tensor o_v, int64_t seed, Tensor uc,
                int64_t ep, int64_t off, c10::optional<Tensor> mom, double eps, c10::optional<Tensor> bump_ticket,
                c10::optional<Tensor> o_idx) {
-  const double* momp = nullptr;
-  unsigned int* tk = nullptr;
-  if (bump_ticket.has_value() && bump_ticket->defined()) {
-    need(*bump_ticket, at::kInt, "bump_ticket");
-    tk = reinterpret_cast<unsigned int*>(bump_ticket->data_ptr<int32_t>());
-  }
-  if (mom.has_value() && mom->defined()) {
-    need(*mom, at::kDouble, "mom");
-    TORCH_CHECK(mom->numel() >= 3, "mb_gather: mom needs [count, sum, sum of squares]");
-    momp = ptr<double>(*mom);
-  }
   TORCH_CHECK(obs.is_cuda() && obs.is_contiguous() && obs.scalar_type() == at::kByte, "mb_gather: obs uint8");
-  const bool by_index = o_idx.has_value() && o_idx->defined();
-  TORCH_CHECK(by_index != (o_obs_opt.has_value() && o_obs_opt->defined()), "mb_gather: exactly one of o_obs, o_idx");
-  int64_t* idxp = nullptr;
-  uint8_t* oobs = nullptr;
+  TORCH_CHECK(has(o_idx) != has(o_obs_opt), "mb_gather: exactly one of o_obs, o_idx");
+  const int64_t n = obs.size(0);
+  const int64_t R = obs.numel() / n;
+  aca::MbGatherArgs a{};
   int64_t mb = 0;
-  if (by_index) {
+  if (has(o_idx)) {
     need(*o_idx, at::kLong, "o_idx");
-    idxp = o_idx->data_ptr<int64_t>();
+    a.o_idx = o_idx->data_ptr<int64_t>();
     mb = o_idx->numel();
   } else {
     const Tensor& o_obs = *o_obs_opt;
     TORCH_CHECK(o_obs.is_cuda() && o_obs.is_contiguous() && o_obs.scalar_type() == at::kByte, "mb_gather: o_obs");
-    oobs = o_obs.data_ptr<uint8_t>();
     mb = o_obs.size(0);
+    TORCH_CHECK(o_obs.numel() == mb * R, "mb_gather: o_obs shape");
+    a.o_obs = o_obs.data_ptr<uint8_t>();
   }
   need(act, at::kInt, "act");
   need(o_act, at::kInt, "o_act");
   for (auto* t : {&logp, &adv, &ret, &v, &o_logp, &o_adv, &o_ret, &o_v}) need(*t, at::kFloat, "mb_gather f32");
   TORCH_CHECK(uc.is_cuda() && uc.scalar_type() == at::kLong, "mb_gather: update counter int64");
-  const int64_t n = obs.size(0);
-  const int64_t R = obs.numel() / n;
-  TORCH_CHECK(by_index || o_obs_opt->numel() == mb * R, "mb_gather: o_obs shape");
   TORCH_CHECK(act.numel() == n && logp.numel() == n && adv.numel() == n && ret.numel() == n && v.numel() == n,
               "mb_gather: per-row inputs must have n rows");
   TORCH_CHECK(o_act.numel() == mb && o_logp.numel() == mb && o_adv.numel() == mb && o_ret.numel() == mb &&
                   o_v.numel() == mb, "mb_gather: per-row outputs must have mb rows");
   TORCH_CHECK(off >= 0 && off + mb <= n, "mb_gather: minibatch out of range");
-  check(aca_mb_gather(obs.data_ptr<uint8_t>(), R, ptr<int>(act), ptr<float>(logp), ptr<float>(adv), ptr<float>(ret),
-                      ptr<float>(v), oobs, ptr<int>(o_act), ptr<float>(o_logp),
-                      ptr<float>(o_adv), ptr<float>(o_ret), ptr<float>(o_v), (int)mb, (int)n, (uint32_t)seed,
-                      uc.data_ptr<int64_t>(), (int)ep, (int)off, momp, (float)eps, tk, idxp, cur_stream(obs)),
-        "mb_gather");
+  a.obs = obs.data_ptr<uint8_t>();
+  a.R = R;
+  a.act = ptr<int>(act);
+  a.logp = ptr<float>(logp);
+  a.adv = ptr<float>(adv);
+  a.ret = ptr<float>(ret);
+  a.v = ptr<float>(v);
+  a.o_act = ptr<int>(o_act);
+  a.o_logp = ptr<float>(o_logp);
+  a.o_adv = ptr<float>(o_adv);
+  a.o_ret = ptr<float>(o_ret);
+  a.o_v = ptr<float>(o_v);
+  a.mb = (int)mb;
+  a.n = (int)n;
+  a.seed = (uint32_t)seed;
+  a.uc = uc.data_ptr<int64_t>();
+  a.ep = (int)ep;
+  a.off = (int)off;
+  if (has(mom)) {
+    need(*mom, at::kDouble, "mom");
+    TORCH_CHECK(mom->numel() >= 3, "mb_gather: mom needs [count, sum, sum of squares]");
+    a.mom = ptr<double>(*mom);
+  }
+  a.eps = (float)eps;
+  if (has(bump_ticket)) {
+    need(*bump_ticket, at::kInt, "bump_ticket");
+    a.bump_ticket = reinterpret_cast<unsigned int*>(bump_ticket->data_ptr<int32_t>());
+  }
+  check(aca_mb_gather(&a, cur_stream(obs)), "mb_gather");
 }
 
 void normalize_mom(Tensor a, Tensor out, Tensor mom, double eps) {
@@ -803,7 +743,7 @@ void sumsq(Tensor x, Tensor partial) {
 
 // optional bf16 gradient the optimiser reads in place of g (the all-reduced bf16 comm buffer of the same group)
 const uint16_t* g16_ptr(const c10::optional<Tensor>& g16, const Tensor& p, const char* who) {
-  if (!(g16.has_value() && g16->defined())) return nullptr;
+  if (!has(g16)) return nullptr;
   need(*g16, at::kBFloat16, "g16");
   TORCH_CHECK(g16->numel() == p.numel(), who, ": g16 size mismatch");
   return ptr<uint16_t>(*g16);
@@ -828,14 +768,14 @@ void sumsq_multi(std::vector<Tensor> xs, std::vector<Tensor> partials) {
 
 const float* gnorm_parts_ptr(const c10::optional<Tensor>& parts, double max_norm, const char* who) {
   if (max_norm <= 0) return nullptr;
-  TORCH_CHECK(parts.has_value() && parts->defined(), who, ": max_norm needs the sumsq partials");
+  TORCH_CHECK(has(parts), who, ": max_norm needs the sumsq partials");
   need(*parts, at::kFloat, "gnorm_parts");
   TORCH_CHECK(parts->numel() >= aca_sumsq_parts(), who, ": gnorm_parts too small");
   return ptr<float>(*parts);
 }
 
 uint16_t* shadow_ptr(const c10::optional<Tensor>& shadow, const Tensor& p, const char* who) {
-  if (!(shadow.has_value() && shadow->defined() && shadow->numel() > 0)) return nullptr;
+  if (!(has(shadow) && shadow->numel() > 0)) return nullptr;
   need(*shadow, at::kBFloat16, "shadow");
   TORCH_CHECK(shadow->numel() == p.numel(), who, ": shadow size mismatch");
   return ptr<uint16_t>(*shadow);
@@ -843,47 +783,69 @@ uint16_t* shadow_ptr(const c10::optional<Tensor>& shadow, const Tensor& p, const
 
 // trans: optional CPU int64 [6, 5] table of weight copies the update writes as it goes (optim.hip OptTrans)
 static const int64_t* trans_table(const c10::optional<Tensor>& trans, const char* who) {
-  if (!(trans.has_value() && trans->defined())) return nullptr;
+  if (!has(trans)) return nullptr;
   TORCH_CHECK(!trans->is_cuda() && trans->scalar_type() == at::kLong && trans->is_contiguous() &&
                   trans->numel() == 8 * 5, who, ": trans must be CPU int64 [8, 5]");
   return ptr<int64_t>(*trans);
+}
+
+// the operands Adam and RMSprop share (who: the op, for messages)
+aca::OptStepArgs opt_step_args(const char* who, const Tensor& p, const Tensor& g, const Tensor& v, const Tensor& lr,
+                               const c10::optional<Tensor>& gnorm_parts, const c10::optional<Tensor>& gnorm_out,
+                               const c10::optional<Tensor>& shadow, double eps, double clip, double max_norm,
+                               bool zero_grad, double gmul, double norm_mul, const c10::optional<Tensor>& trans,
+                               const c10::optional<Tensor>& g16) {
+  need(p, at::kFloat, "p");
+  need(g, at::kFloat, "g");
+  need(v, at::kFloat, "v");
+  need(lr, at::kFloat, "lr");
+  TORCH_CHECK(g.numel() == p.numel() && v.numel() == p.numel(), who, ": size mismatch");
+  aca::OptStepArgs a{};
+  a.p = ptr<float>(p);
+  a.g = ptr<float>(g);
+  a.v = ptr<float>(v);
+  a.n = p.numel();
+  a.lr = ptr<float>(lr);
+  a.gnorm_parts = gnorm_parts_ptr(gnorm_parts, max_norm, who);
+  a.gnorm_out = optr<float>(gnorm_out);
+  a.shadow = shadow_ptr(shadow, p, who);
+  a.eps = (float)eps;
+  a.clip = (float)clip;
+  a.max_norm = (float)max_norm;
+  a.zero_grad = zero_grad ? 1 : 0;
+  a.gmul = (float)gmul;
+  a.norm_mul = (float)norm_mul;
+  a.trans = trans_table(trans, who);
+  a.g16 = g16_ptr(g16, p, who);
+  return a;
 }
 
 void adam_step(Tensor p, Tensor g, Tensor m, Tensor v, Tensor lr, Tensor t, c10::optional<Tensor> gnorm_parts,
                c10::optional<Tensor> gnorm_out, c10::optional<Tensor> shadow, double b1, double b2, double eps,
                double clip, double max_norm, Tensor ticket, bool zero_grad, double gmul, double norm_mul,
                c10::optional<Tensor> trans, c10::optional<Tensor> g16) {
-  need(p, at::kFloat, "p");
-  need(g, at::kFloat, "g");
+  aca::OptStepArgs a = opt_step_args("adam_step", p, g, v, lr, gnorm_parts, gnorm_out, shadow, eps, clip, max_norm,
+                                     zero_grad, gmul, norm_mul, trans, g16);
   need(m, at::kFloat, "m");
-  need(v, at::kFloat, "v");
-  need(lr, at::kFloat, "lr");
   need(t, at::kFloat, "t");
   TORCH_CHECK(ticket.numel() >= 9 * 32, "adam_step: the step ticket needs 9 x 32 words (8 shards + top)");
-  TORCH_CHECK(g.numel() == p.numel() && m.numel() == p.numel() && v.numel() == p.numel(), "adam: size mismatch");
-  check(aca_adam_step(ptr<float>(p), ptr<float>(g), ptr<float>(m), ptr<float>(v), p.numel(), ptr<float>(lr),
-                      ptr<float>(t), gnorm_parts_ptr(gnorm_parts, max_norm, "adam"), optr<float>(gnorm_out),
-                      shadow_ptr(shadow, p, "adam"), (float)b1, (float)b2, (float)eps, (float)clip, (float)max_norm,
-                      ptr<unsigned int>(ticket), zero_grad ? 1 : 0, (float)gmul, (float)norm_mul,
-                      trans_table(trans, "adam_step"), g16_ptr(g16, p, "adam_step"), cur_stream(p)),
-        "adam_step");
+  TORCH_CHECK(m.numel() == p.numel(), "adam_step: size mismatch");
+  a.m = ptr<float>(m);
+  a.t = ptr<float>(t);
+  a.b1 = (float)b1;
+  a.b2 = (float)b2;
+  a.ticket = ptr<unsigned int>(ticket);
+  check(aca_adam_step(&a, cur_stream(p)), "adam_step");
 }
 
 void rmsprop_step(Tensor p, Tensor g, Tensor v, Tensor lr, c10::optional<Tensor> gnorm_parts,
                   c10::optional<Tensor> gnorm_out, c10::optional<Tensor> shadow, double alpha, double eps,
                   double clip, double max_norm, bool zero_grad, double gmul, double norm_mul,
                   c10::optional<Tensor> trans, c10::optional<Tensor> g16) {
-  need(p, at::kFloat, "p");
-  need(g, at::kFloat, "g");
-  need(v, at::kFloat, "v");
-  need(lr, at::kFloat, "lr");
-  TORCH_CHECK(g.numel() == p.numel() && v.numel() == p.numel(), "rmsprop: size mismatch");
-  check(aca_rmsprop_step(ptr<float>(p), ptr<float>(g), ptr<float>(v), p.numel(), ptr<float>(lr),
-                         gnorm_parts_ptr(gnorm_parts, max_norm, "rmsprop"), optr<float>(gnorm_out),
-                         shadow_ptr(shadow, p, "rmsprop"), (float)alpha, (float)eps, (float)clip, (float)max_norm,
-                         zero_grad ? 1 : 0, (float)gmul, (float)norm_mul, trans_table(trans, "rmsprop_step"),
-                         g16_ptr(g16, p, "rmsprop_step"), cur_stream(p)),
-        "rmsprop_step");
+  aca::OptStepArgs a = opt_step_args("rmsprop_step", p, g, v, lr, gnorm_parts, gnorm_out, shadow, eps, clip,
+                                     max_norm, zero_grad, gmul, norm_mul, trans, g16);
+  a.b2 = (float)alpha;
+  check(aca_rmsprop_step(&a, cur_stream(p)), "rmsprop_step");
 }
 
 // ---------------------------------------------------------------------------------------------- MLP engine
@@ -891,7 +853,7 @@ void rmsprop_step(Tensor p, Tensor g, Tensor v, Tensor lr, c10::optional<Tensor>
 // and the training workspace); lds: dynamic LDS bytes computed there for (desc, mode).
 template <typename T>
 const T* copt(const c10::optional<Tensor>& t, at::ScalarType dt, const char* name) {
-  if (!(t.has_value() && t->defined())) return nullptr;
+  if (!has(t)) return nullptr;
   need(*t, dt, name);
   return ptr<T>(*t);
 }
@@ -948,11 +910,11 @@ void ppo_head(Tensor h, Tensor Wh, Tensor bh, Tensor act, Tensor logp_old, Tenso
   a.ticket = reinterpret_cast<unsigned int*>(const_cast<int32_t*>(copt<int32_t>(ticket, at::kInt, "ticket")));
   a.stats = ptr<float>(stats);
   a.B = (int)B;
-  if (hp.has_value() && hp->defined()) {
+  if (has(hp)) {
     need(*hp, at::kFloat, "hp");
     TORCH_CHECK(hp_planes >= 1 && hp_planes <= 4 && hp->numel() >= hp_planes * B * 512,
                 "ppo_head: hp must hold hp_planes (1..4) planes of [B, 512]");
-    TORCH_CHECK(hbias.has_value() && hbias->defined() && hbias->scalar_type() == at::kFloat && hbias->numel() >= 512,
+    TORCH_CHECK(has(hbias) && hbias->scalar_type() == at::kFloat && hbias->numel() >= 512,
                 "ppo_head: hp needs the fp32 fc bias");
     a.hp = ptr<float>(*hp);
     a.hbias = ptr<float>(*hbias);
@@ -969,7 +931,7 @@ int64_t opt_set_unroll(int64_t u) { return aca_opt_set_unroll((int)u); }
 // (None: off); see optim.hip opt_body
 void opt_set_stamps(c10::optional<Tensor> buf) {
   int64_t* p = nullptr;
-  if (buf.has_value() && buf->defined()) {
+  if (has(buf)) {
     need(*buf, at::kLong, "buf");
     p = buf->data_ptr<int64_t>();
   }
@@ -1025,11 +987,11 @@ void mlp_fwd(Tensor desc, int64_t tw_base, int64_t ntw, int64_t mode, int64_t ld
   a.key_shift = (int)key_shift;
   a.seed = (uint32_t)seed;
   const bool gauss = head == 2;
-  if (act_out.has_value() && act_out->defined()) {
+  if (has(act_out)) {
     if (gauss) a.act_f_out = const_cast<float*>(copt<float>(act_out, at::kFloat, "act_out"));
     else a.act_i_out = const_cast<int32_t*>(copt<int32_t>(act_out, at::kInt, "act_out"));
   }
-  if (act_in.has_value() && act_in->defined()) {
+  if (has(act_in)) {
     if (gauss) a.act_f_in = copt<float>(act_in, at::kFloat, "act_in");
     else a.act_i_in = copt<int32_t>(act_in, at::kInt, "act_in");
   }
@@ -1055,7 +1017,7 @@ void mlp_fwd(Tensor desc, int64_t tw_base, int64_t ntw, int64_t mode, int64_t ld
   a.stamps = reinterpret_cast<int64_t*>(stamps_ptr(stamps, 2));   // [2 towers][16 phases]
   // SPEC train path (mlp.hip): hdesc = the CPU copy of desc; taken when both towers have the reference shapes
   int spec = 0;
-  if (hdesc.has_value() && hdesc->defined() && mode == 2 && tw_base == 0 && ntw == 2) {
+  if (has(hdesc) && mode == 2 && tw_base == 0 && ntw == 2) {
     TORCH_CHECK(!hdesc->is_cuda() && hdesc->scalar_type() == at::kLong && hdesc->is_contiguous() &&
                     hdesc->numel() * 8 >= (int64_t)(2 * sizeof(aca::MlpTower)), "mlp_fwd: hdesc must be the CPU desc");
     std::memcpy(a.htw, hdesc->data_ptr(), sizeof(a.htw));
@@ -1105,7 +1067,7 @@ void mlp_wgrad(Tensor items, int64_t nrt, int64_t nsplit, c10::optional<Tensor> 
   need(items, at::kLong, "items");
   TORCH_CHECK(items.dim() == 2 && items.size(1) == 8 && items.size(0) >= 1, "mlp_wgrad: items must be [n, 8]");
   aca::WgradArgs a{};
-  if (bump.has_value() && bump->defined()) {
+  if (has(bump)) {
     need(*bump, at::kLong, "bump");
     a.bump = bump->data_ptr<int64_t>();
   }
@@ -1240,7 +1202,7 @@ void opt_multi(Tensor words, Tensor fvals, c10::optional<Tensor> trans, bool ada
   TORCH_CHECK(!fvals.is_cuda() && fvals.scalar_type() == at::kFloat && fvals.is_contiguous() &&
                   fvals.numel() == words.size(0) * 4, "opt_multi: fvals must be CPU float [nseg, 4]");
   const int64_t* tp = nullptr;
-  if (trans.has_value() && trans->defined()) {
+  if (has(trans)) {
     TORCH_CHECK(!trans->is_cuda() && trans->scalar_type() == at::kLong && trans->is_contiguous() &&
                     trans->numel() == words.size(0) * 8 * 5, "opt_multi: trans must be CPU int64 [nseg, 8, 5]");
     tp = ptr<int64_t>(*trans);
@@ -1361,25 +1323,23 @@ void gemm_big(Tensor A, int64_t lda, bool a_k, Tensor B, int64_t ldb, bool b_k, 
   if (out_mode == 3) {
     TORCH_CHECK(C.is_contiguous() && C.numel() >= std::max<int64_t>(splits, 1) * M * ldc,
                 "gemm_big: out_mode 3 needs splits planes of [M, ldc]");
-    TORCH_CHECK(!(bias.has_value() && bias->defined()) && !relu && !(mask.has_value() && mask->defined()) &&
-                    alpha == 1.0, "gemm_big: partial planes take no epilogue");
+    TORCH_CHECK(!has(bias) && !relu && !has(mask) && alpha == 1.0, "gemm_big: partial planes take no epilogue");
   }
   AcaGemmDesc d{};
   d.A = A.data_ptr();
   d.B = B.data_ptr();
   d.C = C.data_ptr();
-  if (bias.has_value() && bias->defined()) {
+  if (has(bias)) {
     TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->numel() >= N, "gemm_big: bias must be fp32 [N]");
     d.bias = ptr<float>(*bias);
   }
-  if (mask.has_value() && mask->defined()) {
+  if (has(mask)) {
     TORCH_CHECK(mask->scalar_type() == at::kBFloat16, "gemm_big: mask must be bf16");
     check_extent(*mask, M, N, ldm, "mask");
     d.mask = mask->data_ptr();
   }
   if (splits > 1 && out_mode != 3) {
-    TORCH_CHECK(ws.has_value() && ws->defined() && tickets.has_value() && tickets->defined(),
-                "gemm_big: split-K needs ws and tickets");
+    TORCH_CHECK(has(ws) && has(tickets), "gemm_big: split-K needs ws and tickets");
     TORCH_CHECK(ws->scalar_type() == at::kFloat && ws->numel() >= aca_gemm_big_ws((int)M, (int)N, (int)splits),
                 "gemm_big: ws too small");
     TORCH_CHECK(tickets->scalar_type() == at::kInt &&
@@ -1395,7 +1355,7 @@ void gemm_big(Tensor A, int64_t lda, bool a_k, Tensor B, int64_t ldb, bool b_k, 
   d.alpha = (float)alpha;
   d.splits = (int)splits;
   d.tile = (int)variant;
-  if (stamps.has_value() && stamps->defined()) {
+  if (has(stamps)) {
     const int64_t grid = ((M + 127) / 128) * ((N + 127) / 128) * std::max<int64_t>(splits, 1);
     TORCH_CHECK(stamps->scalar_type() == at::kLong && stamps->numel() >= grid * 8, "gemm_big: stamps [grid, 8] int64");
     d.stamps = reinterpret_cast<unsigned long long*>(stamps->data_ptr<int64_t>());
@@ -1413,8 +1373,7 @@ void gemm(Tensor A, int64_t lda, bool a_k, Tensor B, int64_t ldb, bool b_k, Tens
           c10::optional<Tensor> stamps, c10::optional<Tensor> colsum_part) {
   TORCH_CHECK(out_mode >= 0 && out_mode <= 3, "gemm: bad out_mode");
   if (out_mode == 3)
-    TORCH_CHECK(!(bias.has_value() && bias->defined()) && !relu && !(mask.has_value() && mask->defined()) &&
-                    !(colsum.has_value() && colsum->defined()),
+    TORCH_CHECK(!has(bias) && !relu && !has(mask) && !has(colsum),
                 "gemm: out_mode 3 (partial planes) takes no bias / relu / mask / colsum");
   TORCH_CHECK(aca_gemm_supported((int)tile, (int)bk), "gemm: unsupported tile ", tile, " / bk ", bk);
   TORCH_CHECK(C.scalar_type() == (out_mode == 1 ? at::kBFloat16 : at::kFloat), "gemm: C dtype mismatch");
@@ -1463,21 +1422,20 @@ void gemm(Tensor A, int64_t lda, bool a_k, Tensor B, int64_t ldb, bool b_k, Tens
   }
   if (out_mode == 3) check_extent(C, aca_gemm_effective_splits((int)K, (int)bk, (int)splits) * M, N, ldc, "C");
   else check_extent(C, M, N, ldc, "C");
-  if (bias.has_value() && bias->defined()) {
+  if (has(bias)) {
     TORCH_CHECK(bias->scalar_type() == at::kFloat && bias->numel() >= N, "gemm: bias must be fp32 [N]");
   }
-  if (mask.has_value() && mask->defined()) {
+  if (has(mask)) {
     TORCH_CHECK(mask->scalar_type() == at::kBFloat16, "gemm: mask must be bf16");
     check_extent(*mask, M, N, ldm, "mask");
   }
-  if (colsum.has_value() && colsum->defined()) {
+  if (has(colsum)) {
     TORCH_CHECK(colsum->scalar_type() == at::kFloat && colsum->numel() >= (colsum_mod > 0 ? colsum_mod : N),
                 "gemm: colsum too small");
   }
   const int eff = aca_gemm_effective_splits((int)K, (int)bk, (int)splits);
   if (eff > 1 && out_mode < 2) {
-    TORCH_CHECK(ws.has_value() && ws->defined() && tickets.has_value() && tickets->defined(),
-                "gemm: slab split-K needs ws and tickets");
+    TORCH_CHECK(has(ws) && has(tickets), "gemm: slab split-K needs ws and tickets");
     int bm, bn;
     aca_gemm_tile_dims((int)tile, &bm, &bn);
     const int64_t tiles = ((M + bm - 1) / bm) * ((N + bn - 1) / bn);
@@ -1489,14 +1447,14 @@ void gemm(Tensor A, int64_t lda, bool a_k, Tensor B, int64_t ldb, bool b_k, Tens
   }
   d.A = A.data_ptr(); d.B = B.data_ptr(); d.C = C.data_ptr();
   d.bias = optr<float>(bias);
-  d.mask = (mask.has_value() && mask->defined()) ? mask->data_ptr() : nullptr;
+  d.mask = has(mask) ? mask->data_ptr() : nullptr;
   d.colsum = optr<float>(colsum);
   d.lda = lda; d.ldb = ldb; d.ldc = ldc; d.ldm = ldm;
   d.M = (int)M; d.N = (int)N; d.K = (int)K;
   d.a_k = a_k; d.b_k = b_k;
   d.out_mode = (int)out_mode; d.relu = relu ? 1 : 0; d.colsum_mod = (int)colsum_mod;
   d.alpha = (float)alpha;
-  if (stamps.has_value() && stamps->defined()) {   // diagnostics: [tiles * splits, 4] int64 per workgroup
+  if (has(stamps)) {   // diagnostics: [tiles * splits, 4] int64 per workgroup
     int bm, bn;
     aca_gemm_tile_dims((int)tile, &bm, &bn);
     const int64_t wgs = ((M + bm - 1) / bm) * ((N + bn - 1) / bn) * aca_gemm_effective_splits((int)K, (int)bk, (int)splits);
@@ -1505,7 +1463,7 @@ void gemm(Tensor A, int64_t lda, bool a_k, Tensor B, int64_t ldb, bool b_k, Tens
     d.stamps = ptr<unsigned long long>(*stamps);
   }
   d.tile = (int)tile; d.bk = (int)bk; d.splits = (int)splits;
-  if (colsum_part.has_value() && colsum_part->defined()) {
+  if (has(colsum_part)) {
     TORCH_CHECK(d.colsum && eff == 1 && out_mode != 3, "gemm: colsum partials need colsum and no split-K");
     int bm, bn;
     aca_gemm_tile_dims((int)tile, &bm, &bn);
@@ -1554,10 +1512,6 @@ void gemm_group_pause(bool paused) {   // autotuning inside an open group launch
   }
 }
 
-int64_t gemm_effective_splits(int64_t K, int64_t bk, int64_t splits) {
-  return aca_gemm_effective_splits((int)K, (int)bk, (int)splits);
-}
-
 // Fused Nature-CNN trunk (conv1..conv3 of one env per workgroup, csrc/kernels/cnn_fused.hip). Shapes are fixed by
 // the kernel: obs [B, 4, 84, 84] uint8, W1 [32, 256] (OIHW), W2 [64, 512] / W3 [64, 576] (OHWI), y1 [B*400, 32],
 // y2 [B*81, 64], y3 [B*49, 64]; all 16-byte aligned (the kernel uses 16-byte vector accesses).
@@ -1567,59 +1521,40 @@ void cnn_trunk_fwd(Tensor obs, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tenso
                    Tensor y2, Tensor y3, double scale, c10::optional<Tensor> shift_out,
                    c10::optional<Tensor> stamps, int64_t mode, c10::optional<Tensor> copy_out,
                    c10::optional<Tensor> obs_idx) {
+  const char* op = "cnn_trunk_fwd";
   need(obs, at::kByte, "obs");
-  for (auto* w : {&W1, &W2, &W3, &y1, &y2, &y3}) need(*w, at::kBFloat16, "trunk bf16 operand");
-  for (auto* b : {&b1, &b2, &b3}) need(*b, at::kFloat, "trunk bias");
   TORCH_CHECK(obs.numel() % (4 * 84 * 84) == 0, "cnn_trunk_fwd: obs must be [B, 4, 84, 84]");
   int64_t B = obs.numel() / (4 * 84 * 84);
   const int64_t* idxp = nullptr;
-  if (obs_idx.has_value() && obs_idx->defined()) {   // sample b = row obs_idx[b] of obs (per-env modes 3 / 5)
+  if (has(obs_idx)) {   // sample b = row obs_idx[b] of obs (per-env modes 3 / 5)
     need(*obs_idx, at::kLong, "obs_idx");
     TORCH_CHECK(mode == 3 || mode == 5, "cnn_trunk_fwd: obs_idx needs a per-env mode");
     B = obs_idx->numel();
     idxp = obs_idx->data_ptr<int64_t>();
   }
-  TORCH_CHECK(W1.numel() == 32 * 256 && W2.numel() == 64 * 512 && W3.numel() == 64 * 576,
-              "cnn_trunk_fwd: weights must be Nature-CNN conv1..3");
-  TORCH_CHECK(b1.numel() == 32 && b2.numel() == 64 && b3.numel() == 64, "cnn_trunk_fwd: bias sizes");
-  TORCH_CHECK(y1.numel() >= B * 400 * 32 && y2.numel() >= B * 81 * 64 && y3.numel() >= B * 49 * 64,
-              "cnn_trunk_fwd: activation buffers too small");
-  for (auto* t : {&obs, &W1, &W2, &W3, &y1, &y2, &y3})
-    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0, "cnn_trunk_fwd: operands must be 16B aligned");
-  uint8_t* so = nullptr;
-  if (shift_out.has_value() && shift_out->defined()) {
-    need(*shift_out, at::kByte, "shift_out");
-    TORCH_CHECK(shift_out->numel() == obs.numel() && reinterpret_cast<uintptr_t>(shift_out->data_ptr()) % 16 == 0 &&
-                    shift_out->data_ptr() != obs.data_ptr(),
-                "cnn_trunk_fwd: shift_out must be a distinct, aligned [B, 4, 84, 84] uint8 buffer");
-    so = ptr<uint8_t>(*shift_out);
-  }
+  const aca::TrunkArgs tr = trunk_args(op, W1, b1, W2, b2, W3, b3, y1, y2, y3, scale, shift_out, obs, B, false);
+  TORCH_CHECK(aligned16(obs), "cnn_trunk_fwd: operands must be 16B aligned");
+  const bool rows = mode == 1 || mode == 2 || mode == 6 || mode == 7;
   uint8_t* co = nullptr;
-  if (copy_out.has_value() && copy_out->defined()) {
-    TORCH_CHECK(mode == 1 || mode == 2 || mode == 6 || mode == 7, "cnn_trunk_fwd: copy_out needs a row-split mode");
+  if (has(copy_out)) {
+    TORCH_CHECK(rows, "cnn_trunk_fwd: copy_out needs a row-split mode");
     need(*copy_out, at::kByte, "copy_out");
-    TORCH_CHECK(copy_out->numel() == obs.numel() && reinterpret_cast<uintptr_t>(copy_out->data_ptr()) % 16 == 0 &&
-                    copy_out->data_ptr() != obs.data_ptr(),
+    TORCH_CHECK(copy_out->numel() == obs.numel() && aligned16(*copy_out) && copy_out->data_ptr() != obs.data_ptr(),
                 "cnn_trunk_fwd: copy_out must be a distinct, aligned [B, 4, 84, 84] uint8 buffer");
     co = ptr<uint8_t>(*copy_out);
   }
-  if (mode == 1 || mode == 2 || mode == 6 || mode == 7) {
+  if (rows) {
     // 2: the row kernel with its conv2/conv3 weight loads issued after conv1; 6 / 7: modes 1 / 2 reading
     // fragment-ordered W2 / W3 copies (W1 row-major)
-    check(aca_cnn_trunk_rows(ptr<uint8_t>(obs), ptr<uint16_t>(W1), ptr<float>(b1), ptr<uint16_t>(W2),
-                             ptr<float>(b2), ptr<uint16_t>(W3), ptr<float>(b3), ptr<uint16_t>(y1), ptr<uint16_t>(y2),
-                             ptr<uint16_t>(y3), (int)B, (float)scale, so, co, stamps_ptr(stamps, B * 7),
+    check(aca_cnn_trunk_rows(ptr<uint8_t>(obs), &tr, (int)B, co, stamps_ptr(stamps, B * 7),
                              (mode == 2 || mode == 7) ? 1 : 0, mode >= 6 ? 1 : 0, cur_stream(obs)),
           "cnn_trunk_rows");
     return;
   }
   if (mode == 3 || mode == 5) {   // the per-env bf16-staged kernel (one byte conversion per pixel); mode 5: W1..W3
     // are the fragment-ordered copies (frag_weights)
-    TORCH_CHECK(!stamps.has_value() || !stamps->defined(), "cnn_trunk_fwd: mode 3 has no phase stamps");
-    check(aca_cnn_trunk_fwd_s16(ptr<uint8_t>(obs), ptr<uint16_t>(W1), ptr<float>(b1), ptr<uint16_t>(W2),
-                                ptr<float>(b2), ptr<uint16_t>(W3), ptr<float>(b3), ptr<uint16_t>(y1),
-                                ptr<uint16_t>(y2), ptr<uint16_t>(y3), (int)B, (float)scale, so, idxp,
-                                mode == 5 ? 1 : 0, cur_stream(obs)),
+    TORCH_CHECK(!has(stamps), "cnn_trunk_fwd: mode 3 has no phase stamps");
+    check(aca_cnn_trunk_fwd_s16(ptr<uint8_t>(obs), &tr, (int)B, idxp, mode == 5 ? 1 : 0, cur_stream(obs)),
           "cnn_trunk_fwd_s16");
     return;
   }
@@ -1648,33 +1583,37 @@ void cnn_trunk_bwd(Tensor dy3, Tensor W3, Tensor y2, Tensor W2, Tensor y1, Tenso
                   dy1.numel() >= B * 400 * 32 && biasp.numel() >= B * 160,
               "cnn_trunk_bwd: buffers too small");
   TORCH_CHECK(!bias_acc || persist > 0, "cnn_trunk_bwd: bias_acc needs the persistent kernel");
-  const uint8_t* wo = nullptr;
-  const int64_t* wi = nullptr;
-  float* wp = nullptr;
-  if (w1_obs.has_value() && w1_obs->defined()) {
+  aca::TrunkBwdArgs a{};
+  if (has(w1_obs)) {
     need(*w1_obs, at::kByte, "w1_obs");
     TORCH_CHECK(w1_obs->is_contiguous() && w1_obs->numel() % (4 * 84 * 84) == 0, "cnn_trunk_bwd: w1_obs [*, 4, 84, 84]");
-    TORCH_CHECK(w1_planes.has_value() && w1_planes->defined(), "cnn_trunk_bwd: w1_obs needs w1_planes");
+    TORCH_CHECK(has(w1_planes), "cnn_trunk_bwd: w1_obs needs w1_planes");
     need(*w1_planes, at::kFloat, "w1_planes");
     const int64_t np = persist > 0 ? std::min<int64_t>(persist, B) : B;   // one plane per workgroup
     TORCH_CHECK(w1_planes->numel() >= np * 32 * 256, "cnn_trunk_bwd: w1_planes needs a [32][256] plane per workgroup");
-    if (w1_obs_idx.has_value() && w1_obs_idx->defined()) {
+    if (has(w1_obs_idx)) {
       need(*w1_obs_idx, at::kLong, "w1_obs_idx");
       TORCH_CHECK(w1_obs_idx->numel() >= B, "cnn_trunk_bwd: w1_obs_idx needs B rows");
-      wi = ptr<int64_t>(*w1_obs_idx);
+      a.w1.obs_idx = ptr<int64_t>(*w1_obs_idx);
     } else {
       TORCH_CHECK(w1_obs->numel() >= B * 4 * 84 * 84, "cnn_trunk_bwd: w1_obs needs B samples");
     }
-    wo = ptr<uint8_t>(*w1_obs);
-    wp = ptr<float>(*w1_planes);
+    a.w1.obs = ptr<uint8_t>(*w1_obs);
+    a.w1.planes = ptr<float>(*w1_planes);
+    a.w1.scale = (float)w1_scale;
   }
-  TORCH_CHECK(!skip_dy1 || (wo && persist > 0), "cnn_trunk_bwd: skip_dy1 needs the persistent conv1 fold");
-  check(aca_cnn_trunk_bwd(ptr<uint16_t>(dy3), ptr<uint16_t>(W3), ptr<uint16_t>(y2), ptr<uint16_t>(W2),
-                          ptr<uint16_t>(y1), ptr<uint16_t>(dy2), skip_dy1 ? nullptr : ptr<uint16_t>(dy1),
-                          ptr<float>(biasp), (int)B,
-                          stamps_ptr(stamps, B), (int)persist, wo, wi, wp, (float)w1_scale, bias_acc ? 1 : 0,
-                          cur_stream(dy3)),
-        "cnn_trunk_bwd");
+  TORCH_CHECK(!skip_dy1 || (a.w1.obs && persist > 0), "cnn_trunk_bwd: skip_dy1 needs the persistent conv1 fold");
+  a.dy3 = ptr<uint16_t>(dy3);
+  a.W3 = ptr<uint16_t>(W3);
+  a.y2 = ptr<uint16_t>(y2);
+  a.W2 = ptr<uint16_t>(W2);
+  a.y1 = ptr<uint16_t>(y1);
+  a.dy2 = ptr<uint16_t>(dy2);
+  a.dy1 = skip_dy1 ? nullptr : ptr<uint16_t>(dy1);
+  a.biasp = ptr<float>(biasp);
+  a.B = (int)B;
+  a.stamps = stamps_ptr(stamps, B);
+  check(aca_cnn_trunk_bwd(&a, (int)persist, bias_acc ? 1 : 0, cur_stream(dy3)), "cnn_trunk_bwd");
 }
 
 // Gradient finaliser (optim.hip grad_finalize_kernel): jobs = device int64 [njobs, 8] (dst, src, n, stride, S,
@@ -1691,7 +1630,7 @@ void grad_finalize(Tensor jobs, Tensor partial, c10::optional<Tensor> spart, int
               "grad_finalize: partial too small / too many jobs");
   const double* sp = nullptr;
   int sN = 0, sppo = 0;
-  if (spart.has_value() && spart->defined()) {
+  if (has(spart)) {
     need(*spart, at::kDouble, "spart");
     TORCH_CHECK(spart->dim() == 2 && (spart->size(1) == 10 || spart->size(1) == aca::PH_NSTAT) && B >= 1 &&
                     ent_coef.has_value() && kl_coef.has_value() && stats.has_value() && stats->numel() >= 8,
@@ -1709,6 +1648,66 @@ void grad_finalize(Tensor jobs, Tensor partial, c10::optional<Tensor> spart, int
         "grad_finalize");
 }
 
+// The operands the three A2C learner heads share, validated (loss_args.h HeadBwdArgs; B is set by the launcher):
+// rollout [T, N], z [>= B, A + 1] contiguous, h / dh [>= B, 512], Wh [512, A + 1]. exact: val is exactly [T + 1, N]
+// and dones [T, N].
+aca::HeadBwdArgs head_args(const char* op, bool exact, const Tensor& z, const Tensor& act, const Tensor& logp_old,
+                           const Tensor& ent_coef, const Tensor& kl_coef, double vf_coef, const Tensor& rew,
+                           const Tensor& val, const Tensor& dones, int64_t L, int64_t returns_mode, bool norm_adv,
+                           double gamma, double lam, const Tensor& ret_w, const Tensor& adv_w, const Tensor& h,
+                           const Tensor& Wh, const Tensor& dh) {
+  TORCH_CHECK(rew.dim() == 2, op, ": rewards must be [T, N]");
+  const int64_t T = rew.size(0), N = rew.size(1), B = T * N;
+  TORCH_CHECK(z.dim() == 2 && z.size(0) >= B, op, ": z must be [B, A + 1]");
+  const int64_t A1 = z.size(1);
+  need(z, at::kFloat, "z");
+  need(act, at::kInt, "act");
+  need(dones, at::kByte, "dones");
+  for (const Tensor* t : {&logp_old, &ent_coef, &kl_coef, &rew, &val, &ret_w, &adv_w})
+    need(*t, at::kFloat, "head fp32 operand");
+  for (const Tensor* t : {&h, &Wh, &dh}) need(*t, at::kBFloat16, "head bf16 operand");
+  TORCH_CHECK(z.is_contiguous() && z.stride(0) == A1, op, ": z must be contiguous [B, A + 1]");
+  TORCH_CHECK(exact ? (val.numel() == (T + 1) * N && dones.numel() == B)
+                    : (val.numel() >= (T + 1) * N && dones.numel() >= B), op, ": shape mismatch (val, dones)");
+  TORCH_CHECK(act.numel() >= B && logp_old.numel() >= B && ret_w.numel() >= B && adv_w.numel() >= B &&
+                  h.numel() >= B * 512 && dh.numel() >= B * 512 && Wh.numel() == 512 * A1, op, ": shape mismatch");
+  aca::HeadBwdArgs a{};
+  a.z = ptr<float>(z);
+  a.act = ptr<int32_t>(act);
+  a.logp_old = ptr<float>(logp_old);
+  a.ent_coef = ptr<float>(ent_coef);
+  a.kl_coef = ptr<float>(kl_coef);
+  a.vf_coef = (float)vf_coef;
+  a.rew = ptr<float>(rew);
+  a.val = ptr<float>(val);
+  a.dn = ptr<uint8_t>(dones);
+  a.T = (int)T;
+  a.N = (int)N;
+  a.L = (int)L;
+  a.returns_mode = (int)returns_mode;
+  a.norm_adv = norm_adv ? 1 : 0;
+  a.gamma = (float)gamma;
+  a.lam = (float)lam;
+  a.ret_w = ptr<float>(ret_w);
+  a.adv_w = ptr<float>(adv_w);
+  a.h = ptr<uint16_t>(h);
+  a.Wh = ptr<uint16_t>(Wh);
+  a.dh = ptr<uint16_t>(dh);
+  return a;
+}
+
+// gradient slots and statistics of head_bwd / a2c_head (written directly)
+void head_grads(const char* op, aca::HeadBwdArgs& a, int64_t A1, const Tensor& gWh, const Tensor& gbh,
+                const Tensor& gbfc, const Tensor& stats) {
+  for (const Tensor* t : {&gWh, &gbh, &gbfc, &stats}) need(*t, at::kFloat, "head fp32 operand");
+  TORCH_CHECK(gWh.numel() == 512 * A1 && gbh.numel() == A1 && gbfc.numel() == 512 && stats.numel() >= 8,
+              op, ": shape mismatch (gradient slots, stats)");
+  a.gWh = ptr<float>(gWh);
+  a.gbh = ptr<float>(gbh);
+  a.gbfc = ptr<float>(gbfc);
+  a.stats = ptr<float>(stats);
+}
+
 // A2C learner head, one workgroup per env (loss.hip a2c_head_env_kernel; A2C without advantage normalisation): the
 // bootstrap value V(s_T) from the rollout's last fc planes (written into val[T]), returns, loss, dz, dh, and per-env
 // partial planes of dWh [N, 512 * A1], dbfc [N, 512], dbh [N, A1] + statistics rows spart [N, 10] (reduced by the
@@ -1718,46 +1717,33 @@ void a2c_head_env(Tensor z, Tensor act, Tensor logp_old, Tensor ent_coef, Tensor
                   Tensor adv_w, Tensor h, Tensor Wh, Tensor dh, c10::optional<Tensor> hpart, int64_t S,
                   c10::optional<Tensor> bfc, c10::optional<Tensor> bh, Tensor pWh, Tensor pbfc, Tensor pbh,
                   Tensor spart, c10::optional<Tensor> stamps) {
-  TORCH_CHECK(rew.dim() == 2, "a2c_head_env: rewards must be [T, N]");
-  const int T = rew.size(0), N = rew.size(1), B = T * N;
-  TORCH_CHECK(z.dim() == 2 && z.size(0) >= B, "a2c_head_env: z must be [B, A + 1]");
-  const int A = z.size(1) - 1, A1 = A + 1;
-  need(z, at::kFloat, "z");
-  need(act, at::kInt, "act");
-  need(dones, at::kByte, "dones");
-  for (auto* t : {&logp_old, &ent_coef, &kl_coef, &rew, &val, &ret_w, &adv_w, &pWh, &pbfc, &pbh})
-    need(*t, at::kFloat, "a2c_head_env fp32 operand");
+  const char* op = "a2c_head_env";
+  aca::A2cEnvArgs a{};
+  a.h = head_args(op, false, z, act, logp_old, ent_coef, kl_coef, vf_coef, rew, val, dones, L, returns_mode, false,
+                  gamma, lam, ret_w, adv_w, h, Wh, dh);
+  const int64_t N = a.h.N, A1 = z.size(1);
+  for (const Tensor* t : {&pWh, &pbfc, &pbh}) need(*t, at::kFloat, "a2c_head_env fp32 operand");
   need(spart, at::kDouble, "spart");
-  for (auto* t : {&h, &Wh, &dh}) need(*t, at::kBFloat16, "a2c_head_env bf16 operand");
-  TORCH_CHECK(z.is_contiguous() && z.stride(0) == A1, "a2c_head_env: z must be contiguous [B, A + 1]");
-  TORCH_CHECK(act.numel() >= B && logp_old.numel() >= B && val.numel() >= (int64_t)(T + 1) * N &&
-                  dones.numel() >= B && ret_w.numel() >= B && adv_w.numel() >= B && h.numel() >= (int64_t)B * 512 &&
-                  dh.numel() >= (int64_t)B * 512 && Wh.numel() == 512 * A1,
-              "a2c_head_env: shape mismatch");
-  TORCH_CHECK(pWh.numel() >= (int64_t)N * 512 * A1 && pbfc.numel() >= (int64_t)N * 512 && pbh.numel() >= (int64_t)N * A1 &&
-                  spart.numel() >= (int64_t)N * 10,
-              "a2c_head_env: partial planes too small");
+  TORCH_CHECK(pWh.numel() >= N * 512 * A1 && pbfc.numel() >= N * 512 && pbh.numel() >= N * A1 &&
+                  spart.numel() >= N * 10, "a2c_head_env: partial planes too small");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(pbfc.data_ptr()) % 8 == 0, "a2c_head_env: pbfc must be 8-byte aligned");
-  const float* hp = nullptr;
-  int64_t pstride = 0;
-  if (hpart.has_value() && hpart->defined()) {
-    need(*hpart, at::kFloat, "hpart");
-    TORCH_CHECK(bfc.has_value() && bh.has_value(), "a2c_head_env: hpart needs bfc and bh");
-    need(*bfc, at::kFloat, "bfc");
+  const aca::FcParts fc = fc_parts(op, hpart, S, bfc, N);
+  if (fc.hpart) {
+    TORCH_CHECK(has(bh), "a2c_head_env: hpart needs bfc and bh");
     need(*bh, at::kFloat, "bh");
-    pstride = hpart->numel() / 32;
-    TORCH_CHECK(hpart->numel() % 32 == 0 && pstride >= (int64_t)N * 512 && S >= 1 && S <= 32,
-                "a2c_head_env: hpart must hold 32 planes of [N, 512]");
-    TORCH_CHECK(bfc->numel() == 512 && bh->numel() == A1, "a2c_head_env: bad bootstrap operands");
-    hp = ptr<float>(*hpart);
+    TORCH_CHECK(bh->numel() == A1, "a2c_head_env: bad bootstrap operands");
+    a.hpart = fc.hpart;
+    a.S = fc.S;
+    a.plane_stride = fc.plane_stride;
+    a.bfc = fc.bfc;
+    a.bh = ptr<float>(*bh);
   }
-  check(aca_a2c_head_env(ptr<float>(z), ptr<int32_t>(act), ptr<float>(logp_old), ptr<float>(ent_coef),
-                         ptr<float>(kl_coef), (float)vf_coef, ptr<float>(rew), ptr<float>(val), ptr<uint8_t>(dones), T,
-                         N, (int)L, (int)returns_mode, (float)gamma, (float)lam, ptr<float>(ret_w), ptr<float>(adv_w),
-                         ptr<uint16_t>(h), ptr<uint16_t>(Wh), ptr<uint16_t>(dh), A, hp, (int)S, pstride,
-                         optr<float>(bfc), optr<float>(bh), ptr<float>(pWh), ptr<float>(pbfc), ptr<float>(pbh),
-                         spart.data_ptr<double>(), stamps_ptr(stamps, N), cur_stream(z)),
-        "a2c_head_env");
+  a.pWh = ptr<float>(pWh);
+  a.pbfc = ptr<float>(pbfc);
+  a.pbh = ptr<float>(pbh);
+  a.spart = spart.data_ptr<double>();
+  a.h.stamps = stamps_ptr(stamps, N);
+  check(aca_a2c_head_env(&a, (int)A1 - 1, cur_stream(z)), op);
 }
 
 // A2C learner head in one launch (loss.hip head_bwd_kernel): returns + EV + advantage normalisation + loss + dz,
@@ -1766,28 +1752,12 @@ void head_bwd(Tensor z, Tensor act, Tensor logp_old, Tensor ent_coef, Tensor kl_
               Tensor val, Tensor dones, int64_t L, int64_t returns_mode, bool norm_adv, double gamma, double lam,
               Tensor ret_w, Tensor adv_w, Tensor h, Tensor Wh, Tensor dh, Tensor gWh, Tensor gbh, Tensor gbfc,
               Tensor stats, c10::optional<Tensor> stamps) {
-  TORCH_CHECK(rew.dim() == 2, "head_bwd: rewards must be [T, N]");
-  const int T = rew.size(0), N = rew.size(1), B = T * N;
-  TORCH_CHECK(z.dim() == 2 && z.size(0) >= B, "head_bwd: z must be [B, A + 1]");
-  const int A = z.size(1) - 1;
-  need(z, at::kFloat, "z");
-  need(act, at::kInt, "act");
-  for (auto* t : {&logp_old, &ent_coef, &kl_coef, &rew, &val, &ret_w, &adv_w, &gWh, &gbh, &gbfc, &stats})
-    need(*t, at::kFloat, "head_bwd fp32 operand");
-  need(dones, at::kByte, "dones");
-  for (auto* t : {&h, &Wh, &dh}) need(*t, at::kBFloat16, "head_bwd bf16 operand");
-  TORCH_CHECK(z.is_contiguous() && z.stride(0) == A + 1, "head_bwd: z must be contiguous [B, A + 1]");
-  TORCH_CHECK(act.numel() >= B && logp_old.numel() >= B && val.numel() == (int64_t)(T + 1) * N &&
-                  dones.numel() == B && ret_w.numel() >= B && adv_w.numel() >= B && h.numel() >= (int64_t)B * 512 &&
-                  dh.numel() >= (int64_t)B * 512 && Wh.numel() == 512 * (A + 1) && gWh.numel() == 512 * (A + 1) &&
-                  gbh.numel() == A + 1 && gbfc.numel() == 512 && stats.numel() >= 8,
-              "head_bwd: shape mismatch");
-  check(aca_head_bwd(ptr<float>(z), ptr<int32_t>(act), ptr<float>(logp_old), ptr<float>(ent_coef),
-                     ptr<float>(kl_coef), (float)vf_coef, ptr<float>(rew), ptr<float>(val), ptr<uint8_t>(dones), T, N,
-                     (int)L, (int)returns_mode, norm_adv ? 1 : 0, (float)gamma, (float)lam, ptr<float>(ret_w),
-                     ptr<float>(adv_w), ptr<uint16_t>(h), ptr<uint16_t>(Wh), ptr<uint16_t>(dh), ptr<float>(gWh),
-                     ptr<float>(gbh), ptr<float>(gbfc), ptr<float>(stats), A, stamps_ptr(stamps, 8), cur_stream(z)),
-        "head_bwd");
+  const char* op = "head_bwd";
+  aca::HeadBwdArgs a = head_args(op, true, z, act, logp_old, ent_coef, kl_coef, vf_coef, rew, val, dones, L,
+                                 returns_mode, norm_adv, gamma, lam, ret_w, adv_w, h, Wh, dh);
+  head_grads(op, a, z.size(1), gWh, gbh, gbfc, stats);
+  a.stamps = stamps_ptr(stamps, 8);
+  check(aca_head_bwd(&a, (int)z.size(1) - 1, cur_stream(z)), op);
 }
 
 // A2C learner head v2 (loss.hip a2c_head_kernel): the bootstrap value V(s_T) from the rollout's last fc partial planes
@@ -1798,46 +1768,27 @@ void a2c_head(Tensor z, Tensor act, Tensor logp_old, Tensor ent_coef, Tensor kl_
               Tensor ret_w, Tensor adv_w, Tensor h, Tensor Wh, Tensor dh, Tensor gWh, Tensor gbh, Tensor gbfc,
               Tensor stats, c10::optional<Tensor> hpart, int64_t planes, c10::optional<Tensor> bfc,
               c10::optional<Tensor> bh, c10::optional<Tensor> bar, c10::optional<Tensor> stamps) {
-  TORCH_CHECK(rew.dim() == 2, "a2c_head: rewards must be [T, N]");
-  const int T = rew.size(0), N = rew.size(1), B = T * N;
-  TORCH_CHECK(z.dim() == 2 && z.size(0) >= B, "a2c_head: z must be [B, A + 1]");
-  const int A = z.size(1) - 1;
-  need(z, at::kFloat, "z");
-  need(act, at::kInt, "act");
-  for (auto* t : {&logp_old, &ent_coef, &kl_coef, &rew, &val, &ret_w, &adv_w, &gWh, &gbh, &gbfc, &stats})
-    need(*t, at::kFloat, "a2c_head fp32 operand");
-  need(dones, at::kByte, "dones");
-  for (auto* t : {&h, &Wh, &dh}) need(*t, at::kBFloat16, "a2c_head bf16 operand");
-  TORCH_CHECK(z.is_contiguous() && z.stride(0) == A + 1, "a2c_head: z must be contiguous [B, A + 1]");
-  TORCH_CHECK(act.numel() >= B && logp_old.numel() >= B && val.numel() == (int64_t)(T + 1) * N &&
-                  dones.numel() == B && ret_w.numel() >= B && adv_w.numel() >= B && h.numel() >= (int64_t)B * 512 &&
-                  dh.numel() >= (int64_t)B * 512 && Wh.numel() == 512 * (A + 1) && gWh.numel() == 512 * (A + 1) &&
-                  gbh.numel() == A + 1 && gbfc.numel() == 512 && stats.numel() >= 8,
-              "a2c_head: shape mismatch");
-  const float* hp = nullptr;
-  int64_t pstride = 0;
-  unsigned int* barp = nullptr;
-  if (hpart.has_value() && hpart->defined()) {
-    need(*hpart, at::kFloat, "hpart");
-    TORCH_CHECK(bfc.has_value() && bh.has_value() && bar.has_value(), "a2c_head: hpart needs bfc, bh and bar");
-    need(*bfc, at::kFloat, "bfc");
+  const char* op = "a2c_head";
+  aca::A2cHeadArgs a{};
+  a.h = head_args(op, true, z, act, logp_old, ent_coef, kl_coef, vf_coef, rew, val, dones, L, returns_mode, norm_adv,
+                  gamma, lam, ret_w, adv_w, h, Wh, dh);
+  const int64_t A1 = z.size(1);
+  head_grads(op, a.h, A1, gWh, gbh, gbfc, stats);
+  const aca::FcParts fc = fc_parts(op, hpart, planes, bfc, a.h.N);
+  a.S = (int)planes;
+  if (fc.hpart) {
+    TORCH_CHECK(has(bh) && has(bar), "a2c_head: hpart needs bfc, bh and bar");
     need(*bh, at::kFloat, "bh");
     need(*bar, at::kInt, "bar");
-    pstride = hpart->numel() / 32;
-    TORCH_CHECK(hpart->numel() % 32 == 0 && pstride >= (int64_t)N * 512 && planes >= 1 && planes <= 32,
-                "a2c_head: hpart must hold 32 planes of [N, 512]");
-    TORCH_CHECK(bfc->numel() == 512 && bh->numel() == A + 1 && bar->numel() >= 3, "a2c_head: bad bootstrap operands");
-    hp = ptr<float>(*hpart);
-    barp = reinterpret_cast<unsigned int*>(bar->data_ptr<int32_t>());
+    TORCH_CHECK(bh->numel() == A1 && bar->numel() >= 3, "a2c_head: bad bootstrap operands");
+    a.hpart = fc.hpart;
+    a.plane_stride = fc.plane_stride;
+    a.bfc = fc.bfc;
+    a.bh = ptr<float>(*bh);
+    a.bar = reinterpret_cast<unsigned int*>(bar->data_ptr<int32_t>());
   }
-  check(aca_a2c_head(ptr<float>(z), ptr<int32_t>(act), ptr<float>(logp_old), ptr<float>(ent_coef),
-                     ptr<float>(kl_coef), (float)vf_coef, ptr<float>(rew), ptr<float>(val), ptr<uint8_t>(dones), T, N,
-                     (int)L, (int)returns_mode, norm_adv ? 1 : 0, (float)gamma, (float)lam, ptr<float>(ret_w),
-                     ptr<float>(adv_w), ptr<uint16_t>(h), ptr<uint16_t>(Wh), ptr<uint16_t>(dh), ptr<float>(gWh),
-                     ptr<float>(gbh), ptr<float>(gbfc), ptr<float>(stats), A, hp, (int)planes, pstride,
-                     hp ? ptr<float>(*bfc) : nullptr, hp ? ptr<float>(*bh) : nullptr, barp, stamps_ptr(stamps, 32),
-                     cur_stream(z)),
-        "a2c_head");
+  a.h.stamps = stamps_ptr(stamps, 32);
+  check(aca_a2c_head(&a, (int)A1 - 1, cur_stream(z)), op);
 }
 
 void im2col_u8(Tensor x, Tensor col, int64_t kh, int64_t kw, int64_t s, double scale) {
@@ -1869,7 +1820,7 @@ void col2im_nhwc(Tensor dcol, Tensor ymask, Tensor dx, c10::optional<Tensor> col
   const int OH = (H - kh) / s + 1, OW = (W - kw) / s + 1;
   TORCH_CHECK(dcol.numel() >= (int64_t)B * OH * OW * C * kh * kw, "col2im: dcol too small");
   TORCH_CHECK(ymask.numel() >= B * H * W * C && dx.numel() >= B * H * W * C, "col2im: dx/ymask too small");
-  if (colsum.has_value() && colsum->defined())
+  if (has(colsum))
     TORCH_CHECK(colsum->scalar_type() == at::kFloat && colsum->numel() >= C, "col2im: colsum must be fp32 [C]");
   check(aca_col2im_nhwc(ptr<uint16_t>(dcol), ptr<uint16_t>(ymask), ptr<uint16_t>(dx), optr<float>(colsum), B, C, H, W,
                         kh, kw, s, cur_stream(dcol)),
@@ -1941,24 +1892,55 @@ void ac_loss(Tensor logits, int64_t ldl, c10::optional<Tensor> value, int64_t ld
   } else {
     TORCH_CHECK(act_i.has_value(), "ac_loss: categorical needs act_i");
   }
-  if (value.has_value() && value->defined()) {
-    TORCH_CHECK(dvalue.has_value() && dvalue->defined(), "ac_loss: value needs dvalue");
+  if (has(value)) {
+    TORCH_CHECK(has(dvalue), "ac_loss: value needs dvalue");
     check_extent(*value, B, 1, ldv, "value");
     check_extent(*dvalue, B, 1, lddv, "dvalue");
   }
-  int dbn = 0;
-  if (dbias.has_value() && dbias->defined()) {
+  aca::LossArgs a{};
+  a.logits = ptr<float>(logits);
+  a.ldl = ldl;
+  a.value = optr<float>(value);
+  a.ldv = ldv;
+  a.act_i = optr<int32_t>(act_i);
+  a.act_f = optr<float>(act_f);
+  a.log_std = optr<float>(log_std);
+  a.logp_old = ptr<float>(logp_old);
+  a.adv = optr<float>(adv);
+  a.ret = optr<float>(ret);
+  a.v_old = optr<float>(v_old);
+  a.ent_coef = optr<float>(ent_coef);
+  a.kl_coef = optr<float>(kl_coef);
+  a.vf_coef = (float)vf_coef;
+  a.ppo_clip = (float)ppo_clip;
+  a.v_clip = (float)v_clip;
+  a.dlogits = ptr<uint16_t>(dlogits);
+  a.lddl = lddl;
+  a.dvalue = optr<uint16_t>(dvalue);
+  a.lddv = lddv;
+  a.dlog_std = optr<float>(dlog_std);
+  a.stats = ptr<float>(stats);
+  a.B = (int)B;
+  a.A = (int)A;
+  a.gaussian = gaussian ? 1 : 0;
+  a.returns_mode = (int)returns_mode;
+  a.rew = optr<float>(rew);
+  a.val = optr<float>(val);
+  a.dn = optr<uint8_t>(dones);
+  a.T = T;
+  a.N = N;
+  a.L = (int)L;
+  a.gamma = (float)gamma;
+  a.lam = (float)lam;
+  a.norm_adv = norm_adv ? 1 : 0;
+  a.ret_w = optr<float>(ret_w);
+  a.adv_w = optr<float>(adv_w);
+  if (has(dbias)) {
     TORCH_CHECK(dbias->scalar_type() == at::kFloat && dbias->numel() >= A + 1, "ac_loss: dbias must be fp32 [A+1]");
-    dbn = A + 1;
+    a.dbias = ptr<float>(*dbias);
+    a.dbias_n = (int)A + 1;
   }
-  check(aca_ac_loss(ptr<float>(logits), ldl, optr<float>(value), ldv, optr<int32_t>(act_i), optr<float>(act_f),
-                    optr<float>(log_std), ptr<float>(logp_old), optr<float>(adv), optr<float>(ret), optr<float>(v_old),
-                    optr<float>(ent_coef), optr<float>(kl_coef), (float)vf_coef, (float)ppo_clip, (float)v_clip,
-                    ptr<uint16_t>(dlogits), lddl, optr<uint16_t>(dvalue), lddv, optr<float>(dlog_std),
-                    ptr<float>(stats), (int)B, (int)A, gaussian ? 1 : 0, (int)returns_mode, optr<float>(rew),
-                    optr<float>(val), optr<uint8_t>(dones), T, N, (int)L, (float)gamma, (float)lam, norm_adv ? 1 : 0,
-                    optr<float>(ret_w), optr<float>(adv_w), optr<float>(dbias), dbn, cur_stream(logits)),
-        "ac_loss");
+  check(aca_ac_loss(&a, cur_stream(logits)), "ac_loss");
 }
 
 int64_t ping() { return 355; }
@@ -2002,7 +1984,6 @@ TORCH_LIBRARY(acamd, m) {
   m.def("categorical_sample_env(Tensor logits, Tensor tg, Tensor env_ids, int key_shift, int seed, Tensor act, "
         "Tensor logp, Tensor ent, Tensor? vout) -> ()");
   m.def("ev(Tensor x, Tensor y, Tensor out, Tensor? part=None, Tensor? ticket=None) -> ()");
-  m.def("ev_blocks(int n) -> int", &ev_blocks);
   m.def("returns_scan_geometry(int T, int N) -> int[]", &returns_scan_geometry);
   m.def("returns_scan(Tensor r, Tensor v, Tensor d, Tensor ret, Tensor adv, int mode, float gamma, float lam, int L, "
         "bool norm, float eps, Tensor part, Tensor ticket, Tensor mom, Tensor? ev_out=None, Tensor? gz=None) -> ()");
@@ -2059,7 +2040,6 @@ TORCH_LIBRARY(acamd, m) {
         "Tensor? tickets=None, Tensor? stamps=None, int variant=0) -> ()");
   m.def("gemm_big_ws(int M, int N, int splits) -> int", &gemm_big_ws);
   m.def("seg_stats(Tensor x, Tensor segs, Tensor out) -> ()");
-  m.def("gemm_effective_splits(int K, int bk, int splits) -> int", &gemm_effective_splits);
   m.def("cnn_trunk_fwd(Tensor obs, Tensor W1, Tensor b1, Tensor W2, Tensor b2, Tensor W3, Tensor b3, Tensor y1, "
         "Tensor y2, Tensor y3, float scale, Tensor? shift_out=None, Tensor? stamps=None, int mode=3, "
         "Tensor? copy_out=None, Tensor? obs_idx=None) -> ()");

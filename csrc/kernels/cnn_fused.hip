@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "cnn_head.h"
+#include "launch_api.h"
 #include "pong_env.h"
 
 namespace aca {
@@ -782,13 +783,6 @@ __global__ void __launch_bounds__(T_THREADS) cnn_trunk_rows_kernel(
 //   kernel boundary less per rollout step than policy/env kernel + trunk kernel, and the new frame never makes a
 //   global round trip before conv1.
 // ------------------------------------------------------------------------------------------------------------
-struct PongNext {   // the next parity's env state buffers (written by the committing workgroup)
-  float* state;
-  int32_t* tsteps;
-  int64_t* tglob;
-  float* ep_ret;
-};
-
 __device__ __forceinline__ void pong_commit_next(const PongIO& io, const PongNext& nx, int e, const PongOut& r,
                                                  int64_t tg_old) {
   nx.tglob[e] = tg_old + 1;
@@ -1247,14 +1241,7 @@ __device__ __forceinline__ bf16x8 tr_frag(const u16* rows, int ld, int col0, int
 
 // 8 waves (2 per SIMD: one wave per SIMD left every LDS read latency exposed); one workgroup per CU by LDS.
 constexpr int BW_T = 512;
-// The conv1 weight gradient folded into the persistent data-gradient chain (cnn_trunk_bwd_persist_kernel W1G):
-// dW1[o][c] = scale * sum_p dy1[p][o] * obs[ch][4 oy + ky][4 ox + kx], c = (ch, ky, kx), p = (oy, ox).
-struct W1Fold {
-  const uint8_t* obs;        // [*, 4, 84, 84] uint8 frames
-  const int64_t* obs_idx;    // sample b reads obs row obs_idx[b] (null: row b)
-  float* planes;             // [B][32 * 256]
-  float scale;               // 1 / 255
-};
+// (W1Fold, cnn_args.h: the conv1 weight gradient folded into the persistent data-gradient chain)
 constexpr int BW_FR = 4 * 84 * 84;   // frame pixels of a sample (bf16 in LDS: 56.4 KB over the dead W2 rows)
 static_assert(BW_FR + 8 <= BW_RW, "the bf16 frames + a zero chunk fit the weight region");
 static_assert(416 * 32 <= BW_P3E + BW_M2E, "dy1 rows + 16 zero padding rows (13 k-steps of 32) fit the staging");
@@ -1896,31 +1883,27 @@ extern "C" hipError_t aca_fc_value(const float* hpart, int S, int64_t plane_stri
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_cnn_trunk_fwd_s16(const uint8_t* obs, const uint16_t* W1, const float* b1,
-                                            const uint16_t* W2, const float* b2, const uint16_t* W3, const float* b3,
-                                            uint16_t* y1, uint16_t* y2, uint16_t* y3, int B, float scale,
-                                            uint8_t* shift_out, const int64_t* obs_idx, int frag,
-                                            hipStream_t stream) {
+extern "C" hipError_t aca_cnn_trunk_fwd_s16(const uint8_t* obs, const aca::TrunkArgs* tr, int B,
+                                            const int64_t* obs_idx, int frag, hipStream_t stream) {
   if (B <= 0) return hipSuccess;
+  const aca::TrunkArgs& c = *tr;
   if (frag)
-    aca::cnn_trunk_fwd_s16_kernel<true><<<B, 256, 0, stream>>>(obs, W1, b1, W2, b2, W3, b3, y1, y2, y3, scale,
-                                                                shift_out, obs_idx);
+    aca::cnn_trunk_fwd_s16_kernel<true><<<B, 256, 0, stream>>>(obs, c.W1, c.b1, c.W2, c.b2, c.W3, c.b3, c.y1, c.y2,
+                                                                c.y3, c.scale, c.shift_out, obs_idx);
   else
-    aca::cnn_trunk_fwd_s16_kernel<false><<<B, 256, 0, stream>>>(obs, W1, b1, W2, b2, W3, b3, y1, y2, y3, scale,
-                                                                 shift_out, obs_idx);
+    aca::cnn_trunk_fwd_s16_kernel<false><<<B, 256, 0, stream>>>(obs, c.W1, c.b1, c.W2, c.b2, c.W3, c.b3, c.y1, c.y2,
+                                                                 c.y3, c.scale, c.shift_out, obs_idx);
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_cnn_trunk_rows(const uint8_t* obs, const uint16_t* W1, const float* b1, const uint16_t* W2,
-                                         const float* b2, const uint16_t* W3, const float* b3, uint16_t* y1,
-                                         uint16_t* y2, uint16_t* y3, int B, float scale, uint8_t* shift_out,
-                                         uint8_t* copy_out, uint64_t* stamps, int late_w, int frag,
-                                         hipStream_t stream) {
+extern "C" hipError_t aca_cnn_trunk_rows(const uint8_t* obs, const aca::TrunkArgs* tr, int B, uint8_t* copy_out,
+                                         uint64_t* stamps, int late_w, int frag, hipStream_t stream) {
   // frag: W2 / W3 are the fragment-ordered copies (W1 row-major: the kernel stages it through LDS)
   if (B <= 0) return hipSuccess;
+  const aca::TrunkArgs& c = *tr;
 #define ACA_ROWS(LW, FR)                                                                                         \
   aca::cnn_trunk_rows_kernel<LW, FR><<<B * aca::TR_ROWS, aca::T_THREADS, 0, stream>>>(                          \
-      obs, W1, b1, W2, b2, W3, b3, y1, y2, y3, scale, shift_out, copy_out, stamps);
+      obs, c.W1, c.b1, c.W2, c.b2, c.W3, c.b3, c.y1, c.y2, c.y3, c.scale, c.shift_out, copy_out, stamps);
   if (late_w && frag) ACA_ROWS(true, true)
   else if (late_w) ACA_ROWS(true, false)
   else if (frag) ACA_ROWS(false, true)
@@ -1929,61 +1912,53 @@ extern "C" hipError_t aca_cnn_trunk_rows(const uint8_t* obs, const uint16_t* W1,
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_cnn_trunk_bwd(const uint16_t* dy3, const uint16_t* W3, const uint16_t* y2, const uint16_t* W2,
-                                        const uint16_t* y1, uint16_t* dy2, uint16_t* dy1, float* biasp, int B,
-                                        uint64_t* stamps, int persist, const uint8_t* w1_obs,
-                                        const int64_t* w1_obs_idx, float* w1_planes, float w1_scale, int bias_acc,
+extern "C" hipError_t aca_cnn_trunk_bwd(const aca::TrunkBwdArgs* args, int persist, int bias_acc,
                                         hipStream_t stream) {
   // bias_acc (persistent form): one bias-gradient row per workgroup (min(persist, B) rows) instead of one per sample
-  // w1_obs: the conv1 weight gradient folded into the persistent kernel (one [32][256] plane per workgroup)
+  // w1.obs: the conv1 weight gradient folded into the persistent kernel (one [32][256] plane per workgroup)
+  const aca::TrunkBwdArgs& a = *args;
+  const int B = a.B;
   if (B <= 0) return hipSuccess;
-  for (const void* p : {(const void*)dy3, (const void*)W3, (const void*)y2, (const void*)W2, (const void*)y1,
-                        (const void*)dy2, (const void*)dy1})
+  for (const void* p : {(const void*)a.dy3, (const void*)a.W3, (const void*)a.y2, (const void*)a.W2,
+                        (const void*)a.y1, (const void*)a.dy2, (const void*)a.dy1})
     if (reinterpret_cast<uintptr_t>(p) % 16) return hipErrorInvalidValue;
-  if (persist > 0 && w1_obs) {
-    if (!w1_planes || reinterpret_cast<uintptr_t>(w1_obs) % 16) return hipErrorInvalidValue;
-    const aca::W1Fold wf{w1_obs, w1_obs_idx, w1_planes, w1_scale};
+  if (persist > 0 && a.w1.obs) {
+    if (!a.w1.planes || reinterpret_cast<uintptr_t>(a.w1.obs) % 16) return hipErrorInvalidValue;
     aca::cnn_trunk_bwd_persist_kernel<true><<<persist < B ? persist : B, aca::BW_T, 0, stream>>>(
-        dy3, W3, y2, W2, y1, dy2, dy1, biasp, B, stamps, bias_acc, wf);
+        a.dy3, a.W3, a.y2, a.W2, a.y1, a.dy2, a.dy1, a.biasp, B, a.stamps, bias_acc, a.w1);
   } else if (persist > 0) {
     aca::cnn_trunk_bwd_persist_kernel<false><<<persist < B ? persist : B, aca::BW_T, 0, stream>>>(
-        dy3, W3, y2, W2, y1, dy2, dy1, biasp, B, stamps, bias_acc, aca::W1Fold{nullptr, nullptr, nullptr, 0.f});
-  } else if (w1_obs) {
+        a.dy3, a.W3, a.y2, a.W2, a.y1, a.dy2, a.dy1, a.biasp, B, a.stamps, bias_acc, aca::W1Fold{});
+  } else if (a.w1.obs) {
     return hipErrorInvalidValue;   // the conv1 fold is a persistent-kernel feature
   } else {
-    aca::cnn_trunk_bwd_kernel<<<B, aca::BW_T, 0, stream>>>(dy3, W3, y2, W2, y1, dy2, dy1, biasp, stamps);
+    aca::cnn_trunk_bwd_kernel<<<B, aca::BW_T, 0, stream>>>(a.dy3, a.W3, a.y2, a.W2, a.y1, a.dy2, a.dy1, a.biasp,
+                                                           a.stamps);
   }
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_pong_fused_step(
-    uint16_t* h, const float* hpart, int S, int64_t plane_stride, const float* bfc, const uint16_t* Wh,
-    const float* bh, int A, float* z, int32_t* act, float* logp, float* ent, float* value, int key_shift,
-    uint32_t pseed, float* state, int32_t* t, int64_t* tg, float* ep_ret, float* state_n, int32_t* t_n,
-    int64_t* tg_n, float* ep_ret_n, float* ep_stats, const int64_t* ids, const uint8_t* prev, uint8_t* out,
-    float* reward, uint8_t* done, uint8_t* trunc, uint32_t seed, int max_steps, const uint16_t* W1, const float* b1,
-    const uint16_t* W2, const float* b2, const uint16_t* W3, const float* b3, uint16_t* y1, uint16_t* y2,
-    uint16_t* y3, float scale, uint8_t* shift_out, uint64_t* stamps, int frag, int N, hipStream_t stream) {
+extern "C" hipError_t aca_pong_fused_step(const aca::PongIO* pio, const aca::PongNext* nx, const aca::FcParts* fc,
+                                          const aca::PolicyArgs* pol, const aca::TrunkArgs* tr, uint64_t* stamps,
+                                          int frag, int N, hipStream_t stream) {
   // frag: W2 / W3 are the fragment-ordered copies (W1 stays row-major: the kernel stages it through LDS)
   if (N <= 0) return hipSuccess;
-  aca::PongIO io;
-  io.state = state; io.tsteps = t; io.tglob = tg; io.ep_ret = ep_ret; io.ep_stats = ep_stats; io.env_ids = ids;
-  io.prev = prev; io.out = out; io.reward = reward; io.done_out = done; io.trunc_out = trunc; io.seed = seed;
-  io.max_steps = max_steps; io.k = 4;
-  aca::PongNext nx{state_n, t_n, tg_n, ep_ret_n};
-  aca::FcParts fc{hpart, S, plane_stride, bfc};
+  aca::PongIO io = *pio;
+  io.k = 4;
+  const aca::PolicyArgs& p = *pol;
+  const aca::TrunkArgs& c = *tr;
   const int grid = N * aca::TR_ROWS;
-  switch (A + 1) {
+  switch (p.A + 1) {
 #define ACA_FUSED_CASE(A1)                                                                                       \
   case A1:                                                                                                       \
     if (frag)                                                                                                    \
       aca::pong_fused_step_kernel<A1, true><<<grid, aca::T_THREADS, 0, stream>>>(                                \
-          io, nx, fc, h, Wh, bh, z, act, logp, ent, value, key_shift, pseed, W1, b1, W2, b2, W3, b3, y1, y2, y3,  \
-          scale, shift_out, stamps);                                                                             \
+          io, *nx, *fc, p.h, p.Wh, p.bh, p.z, p.act, p.logp, p.ent, p.value, p.key_shift, p.pseed, c.W1, c.b1,   \
+          c.W2, c.b2, c.W3, c.b3, c.y1, c.y2, c.y3, c.scale, c.shift_out, stamps);                               \
     else                                                                                                         \
       aca::pong_fused_step_kernel<A1, false><<<grid, aca::T_THREADS, 0, stream>>>(                               \
-          io, nx, fc, h, Wh, bh, z, act, logp, ent, value, key_shift, pseed, W1, b1, W2, b2, W3, b3, y1, y2, y3,  \
-          scale, shift_out, stamps);                                                                             \
+          io, *nx, *fc, p.h, p.Wh, p.bh, p.z, p.act, p.logp, p.ent, p.value, p.key_shift, p.pseed, c.W1, c.b1,   \
+          c.W2, c.b2, c.W3, c.b3, c.y1, c.y2, c.y3, c.scale, c.shift_out, stamps);                               \
     break;
     ACA_FUSED_CASE(3) ACA_FUSED_CASE(4) ACA_FUSED_CASE(5) ACA_FUSED_CASE(6) ACA_FUSED_CASE(7)
 #undef ACA_FUSED_CASE
@@ -1993,31 +1968,26 @@ extern "C" hipError_t aca_pong_fused_step(
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_pong_fused_env_step(
-    uint16_t* h, const float* hpart, int S, int64_t plane_stride, const float* bfc, const uint16_t* Wh,
-    const float* bh, int A, float* z, int32_t* act, float* logp, float* ent, float* value, int key_shift,
-    uint32_t pseed, float* state, int32_t* t, int64_t* tg, float* ep_ret, float* ep_stats, const int64_t* ids,
-    uint8_t* out, float* reward, uint8_t* done, uint8_t* trunc, uint32_t seed, int max_steps, const uint16_t* W1,
-    const float* b1, const uint16_t* W2, const float* b2, const uint16_t* W3, const float* b3, uint16_t* y1,
-    uint16_t* y2, uint16_t* y3, float scale, uint8_t* shift_out, float* state_n, int32_t* t_n, int64_t* tg_n,
-    float* ep_ret_n, uint64_t* stamps, int frag, int N, hipStream_t stream) {
-  // state_n .. ep_ret_n: the other parity's env state -> two workgroups per env (commit there); null -> one.
+extern "C" hipError_t aca_pong_fused_env_step(const aca::PongIO* pio, const aca::PongNext* nx,
+                                              const aca::FcParts* fc, const aca::PolicyArgs* pol,
+                                              const aca::TrunkArgs* tr, uint64_t* stamps, int frag, int N,
+                                              hipStream_t stream) {
+  // nx: the other parity's env state -> two workgroups per env (commit there); null fields -> one.
   // frag: W2 / W3 are the fragment-ordered copies (W1 stays row-major: LDS-DMA staged)
   if (N <= 0) return hipSuccess;
-  if (S < 1 || S > aca::FC_MAX_PLANES) return hipErrorInvalidValue;
-  const bool split = state_n != nullptr;
-  if (split && (!t_n || !tg_n || !ep_ret_n)) return hipErrorInvalidValue;
-  aca::PongNext nx{state_n, t_n, tg_n, ep_ret_n};
-  aca::PongIO io;
-  io.state = state; io.tsteps = t; io.tglob = tg; io.ep_ret = ep_ret; io.ep_stats = ep_stats; io.env_ids = ids;
-  io.prev = out; io.out = out; io.reward = reward; io.done_out = done; io.trunc_out = trunc; io.seed = seed;
-  io.max_steps = max_steps; io.k = 4;
-  aca::FcParts fc{hpart, S, plane_stride, bfc};
+  if (fc->S < 1 || fc->S > aca::FC_MAX_PLANES) return hipErrorInvalidValue;
+  const bool split = nx->state != nullptr;
+  if (split && (!nx->tsteps || !nx->tglob || !nx->ep_ret)) return hipErrorInvalidValue;
+  aca::PongIO io = *pio;
+  io.prev = io.out;
+  io.k = 4;
+  const aca::PolicyArgs& p = *pol;
+  const aca::TrunkArgs& c = *tr;
 #define ACA_FES_LAUNCH(A1, SPLIT, FRAG, GRID)                                                                   \
   aca::pong_fused_env_step_kernel<A1, SPLIT, FRAG><<<GRID, 256, 0, stream>>>(                                    \
-      io, nx, fc, h, Wh, bh, z, act, logp, ent, value, key_shift, pseed, W1, b1, W2, b2, W3, b3, y1, y2, y3, scale, \
-      shift_out, stamps);
-  switch (A + 1) {
+      io, *nx, *fc, p.h, p.Wh, p.bh, p.z, p.act, p.logp, p.ent, p.value, p.key_shift, p.pseed, c.W1, c.b1, c.W2,  \
+      c.b2, c.W3, c.b3, c.y1, c.y2, c.y3, c.scale, c.shift_out, stamps);
+  switch (p.A + 1) {
 #define ACA_FES_CASE(A1)                                                                                         \
   case A1:                                                                                                       \
     if (split && frag) ACA_FES_LAUNCH(A1, 2, true, 2 * N)                                                      \

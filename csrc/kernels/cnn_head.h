@@ -3,6 +3,7 @@
 // planes in plane order (deterministic), adds the bias, applies ReLU and rounds to bf16 -- exactly the GEMM
 // epilogue it replaces -- and stores the row for the learner, which reuses the rollout's activations.
 #pragma once
+#include "cnn_args.h"
 #include "common.h"
 
 namespace aca {
@@ -12,13 +13,7 @@ constexpr int FC_MAX_PLANES = 32;  // = engine.py FC_PLANES (split-K planes of t
 
 // One workgroup of 256 threads: thread t produces hidden units 2t, 2t+1 of env e (16 planes' loads in flight per
 // round; slots past S read plane 0 and are discarded by a select), bf16-rounded like the GEMM epilogue; stores them
-// if h_out.
-struct FcParts {        // optional: h comes from the fc GEMM's split-K partial planes
-  const float* hpart;    // null: h is read as a finished bf16 row
-  int S;
-  int64_t plane_stride;
-  const float* bfc;
-};
+// if h_out. (The operands travel as FcParts, cnn_args.h.)
 
 // Two-phase form: issue() requests the first round of plane loads (and the bias pair) and returns at once, so a
 // kernel can queue other loads behind them; finish() sums in plane order (further rounds loaded there), exactly as

@@ -9,6 +9,7 @@
 // output pixel) that touched it, applies the ReLU-backward mask of the previous layer's activation and reduces
 // per-channel sums for that layer's bias gradient (LDS atomics, one global atomic per channel per workgroup).
 #include "common.h"
+#include "launch_api.h"
 
 namespace aca {
 

@@ -10,6 +10,7 @@
 // transposing ds_read_b64_tr_b16 WITHOUT materialising it (each lane points its read at the contiguous pixels of its
 // own position / kernel tap).
 #include "common.h"
+#include "launch_api.h"
 
 namespace aca {
 

@@ -7,6 +7,7 @@
 // -ffp-contract=off so the physics rounds exactly like the PyTorch oracle).
 #include "common.h"
 #include "cnn_head.h"
+#include "launch_api.h"
 #include "pong_env.h"
 
 namespace aca {
@@ -123,49 +124,27 @@ __global__ void __launch_bounds__(256) pong_policy_step_kernel(PongIO io, FcPart
 
 }  // namespace aca
 
-static aca::PongIO make_pong_io(float* state, int32_t* t, int64_t* tg, float* ep_ret, float* ep_stats,
-                                const int64_t* ids, const uint8_t* prev, uint8_t* out, float* reward, uint8_t* done,
-                                uint8_t* trunc, uint32_t seed, int max_steps, int k) {
-  aca::PongIO io;
-  io.state = state; io.tsteps = t; io.tglob = tg; io.ep_ret = ep_ret; io.ep_stats = ep_stats; io.env_ids = ids;
-  io.prev = prev; io.out = out; io.reward = reward; io.done_out = done; io.trunc_out = trunc; io.seed = seed;
-  io.max_steps = max_steps; io.k = k;
-  return io;
-}
-
-extern "C" hipError_t aca_env_step_pong(float* state, int32_t* t, int64_t* tg, float* ep_ret, float* ep_stats,
-                                        const int64_t* ids, const int32_t* actions, const uint8_t* prev,
-                                        uint8_t* out, float* reward, uint8_t* done, uint8_t* trunc, uint32_t seed,
-                                        int max_steps, int k, int N, hipStream_t stream) {
+extern "C" hipError_t aca_env_step_pong(const aca::PongIO* io, const int32_t* actions, int N, hipStream_t stream) {
   if (N <= 0) return hipSuccess;
-  aca::PongIO io = make_pong_io(state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed, max_steps,
-                                k);
-  aca::pong_step_kernel<<<N, 256, 0, stream>>>(io, actions);
+  aca::pong_step_kernel<<<N, 256, 0, stream>>>(*io, actions);
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_env_policy_step_pong(uint16_t* h, const float* hpart, int S, int64_t plane_stride,
-                                               const float* bfc, int hdim, const uint16_t* Wh, const float* bh,
-                                               int A, float* z, int32_t* act, float* logp, float* ent, float* value,
-                                               int key_shift, uint32_t pseed, float* state, int32_t* t, int64_t* tg,
-                                               float* ep_ret, float* ep_stats, const int64_t* ids,
-                                               const uint8_t* prev, uint8_t* out, float* reward, uint8_t* done,
-                                               uint8_t* trunc, uint32_t seed, int max_steps, int k, int N,
-                                               int pre_shifted, uint64_t* stamps, hipStream_t stream) {
+extern "C" hipError_t aca_env_policy_step_pong(const aca::PongIO* io, const aca::FcParts* fc,
+                                               const aca::PolicyArgs* pol, int hdim, int N, int pre_shifted,
+                                               uint64_t* stamps, hipStream_t stream) {
   if (N <= 0) return hipSuccess;
-  if (hdim != aca::HEAD_HDIM || reinterpret_cast<uintptr_t>(Wh) % 16 || reinterpret_cast<uintptr_t>(h) % 16)
+  const aca::PolicyArgs& p = *pol;
+  if (hdim != aca::HEAD_HDIM || reinterpret_cast<uintptr_t>(p.Wh) % 16 || reinterpret_cast<uintptr_t>(p.h) % 16)
     return hipErrorInvalidValue;
-  if (hpart && (S < 1 || S > aca::FC_MAX_PLANES || !bfc || reinterpret_cast<uintptr_t>(hpart) % 16 ||
-                reinterpret_cast<uintptr_t>(bfc) % 16 || plane_stride % 4))
+  if (fc->hpart && (fc->S < 1 || fc->S > aca::FC_MAX_PLANES || !fc->bfc || reinterpret_cast<uintptr_t>(fc->hpart) % 16 ||
+                    reinterpret_cast<uintptr_t>(fc->bfc) % 16 || fc->plane_stride % 4))
     return hipErrorInvalidValue;
-  const aca::FcParts fc{hpart, S, plane_stride, bfc};
-  aca::PongIO io = make_pong_io(state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed, max_steps,
-                                k);
-  switch (A + 1) {
-#define ACA_POLICY_CASE(A1)                                                                                         \
-  case A1:                                                                                                          \
-    aca::pong_policy_step_kernel<A1><<<N, 256, 0, stream>>>(io, fc, h, Wh, bh, z, act, logp, ent, value, key_shift,\
-                                                            pseed, pre_shifted, stamps);                            \
+  switch (p.A + 1) {
+#define ACA_POLICY_CASE(A1)                                                                                        \
+  case A1:                                                                                                         \
+    aca::pong_policy_step_kernel<A1><<<N, 256, 0, stream>>>(*io, *fc, p.h, p.Wh, p.bh, p.z, p.act, p.logp, p.ent,  \
+                                                            p.value, p.key_shift, p.pseed, pre_shifted, stamps);   \
     break;
     ACA_POLICY_CASE(3) ACA_POLICY_CASE(4) ACA_POLICY_CASE(5) ACA_POLICY_CASE(6) ACA_POLICY_CASE(7)
     ACA_POLICY_CASE(8) ACA_POLICY_CASE(9) ACA_POLICY_CASE(10) ACA_POLICY_CASE(11) ACA_POLICY_CASE(12)

@@ -6,28 +6,9 @@
 // Oracles: actor_critic_algs_on_tensorflow_amd/envs/classic.py and mujoco.py. This file is compiled with
 // -ffp-contract=off so that fp32 arithmetic rounds exactly like the PyTorch oracle (separately rounded mul/add).
 #include "common.h"
+#include "launch_api.h"
 
 namespace aca {
-
-struct EnvIO {
-  float* state;
-  int32_t* t;
-  int64_t* tg;
-  float* ep_ret;
-  float* ep_stats;  // [sum_ret, count, sum_len]
-  const int64_t* env_ids;
-  const float* prev;  // [N, k*D] frame stack in
-  float* out;         // [N, k*D] frame stack out
-  float* reward;
-  uint8_t* done;
-  uint8_t* truncated;
-  float* final_out;   // optional [N, k*D]: the stack with the transition's new frame BEFORE any auto-reset (the
-                      // terminal observation of a finished episode; time-limit bootstrapping values it)
-  uint32_t seed;
-  int max_steps;
-  int k;
-  int N;
-};
 
 template <int D>
 __device__ __forceinline__ void push_frame_to(const EnvIO& io, float* dst, int i, const float* frame, bool reset) {
@@ -243,49 +224,21 @@ __global__ void __launch_bounds__(256) linear_step_kernel(EnvIO io, const float*
 
 using namespace aca;
 
-static EnvIO make_io(float* state, int32_t* t, int64_t* tg, float* ep_ret, float* ep_stats, const int64_t* ids,
-                     const float* prev, float* out, float* reward, uint8_t* done, uint8_t* trunc, uint32_t seed,
-                     int max_steps, int k, int N, float* final_out = nullptr) {
-  EnvIO io;
-  io.final_out = final_out;
-  io.state = state; io.t = t; io.tg = tg; io.ep_ret = ep_ret; io.ep_stats = ep_stats; io.env_ids = ids;
-  io.prev = prev; io.out = out; io.reward = reward; io.done = done; io.truncated = trunc; io.seed = seed;
-  io.max_steps = max_steps; io.k = k; io.N = N;
-  return io;
-}
-
-extern "C" hipError_t aca_env_step_cartpole(float* state, int32_t* t, int64_t* tg, float* ep_ret, float* ep_stats,
-                                            const int64_t* ids, const int32_t* actions, const float* prev,
-                                            float* out, float* reward, uint8_t* done, uint8_t* trunc,
-                                            uint32_t seed, int max_steps, int k, int N, float* final_out,
-                                            hipStream_t stream) {
-  EnvIO io = make_io(state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed, max_steps, k, N,
-                     final_out);
+extern "C" hipError_t aca_env_step_cartpole(const EnvIO* io, const int32_t* actions, hipStream_t stream) {
   const int bs = 256;
-  cartpole_step_kernel<<<(N + bs - 1) / bs, bs, 0, stream>>>(io, actions);
+  cartpole_step_kernel<<<(io->N + bs - 1) / bs, bs, 0, stream>>>(*io, actions);
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_env_step_pendulum(float* state, int32_t* t, int64_t* tg, float* ep_ret, float* ep_stats,
-                                            const int64_t* ids, const float* actions, int act_dim,
-                                            const float* prev, float* out, float* reward, uint8_t* done,
-                                            uint8_t* trunc, uint32_t seed, int max_steps, int k, int N,
-                                            float* final_out, hipStream_t stream) {
-  EnvIO io = make_io(state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed, max_steps, k, N,
-                     final_out);
+extern "C" hipError_t aca_env_step_pendulum(const EnvIO* io, const float* actions, int act_dim, hipStream_t stream) {
   const int bs = 256;
-  pendulum_step_kernel<<<(N + bs - 1) / bs, bs, 0, stream>>>(io, actions, act_dim);
+  pendulum_step_kernel<<<(io->N + bs - 1) / bs, bs, 0, stream>>>(*io, actions, act_dim);
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_env_step_linear(float* state, int32_t* t, int64_t* tg, float* ep_ret, float* ep_stats,
-                                          const int64_t* ids, const float* actions, const float* A, const float* B,
-                                          const float* prev, float* out, float* reward, uint8_t* done,
-                                          uint8_t* trunc, uint32_t seed, int max_steps, int k, int N,
-                                          float* final_out, hipStream_t stream) {
-  EnvIO io = make_io(state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed, max_steps, k, N,
-                     final_out);
+extern "C" hipError_t aca_env_step_linear(const EnvIO* io, const float* actions, const float* A, const float* B,
+                                          hipStream_t stream) {
   const int bs = 256;
-  linear_step_kernel<<<(N * LIN_LANES + bs - 1) / bs, bs, 0, stream>>>(io, actions, A, B);
+  linear_step_kernel<<<(io->N * LIN_LANES + bs - 1) / bs, bs, 0, stream>>>(*io, actions, A, B);
   return hipGetLastError();
 }

@@ -19,6 +19,7 @@
 // Workgroup order is XCD-grouped per job kind (contiguous tile ranges per XCD), so the tiles sharing y3 / Wfc
 // column blocks meet in one L2.
 #include "common.h"
+#include "launch_api.h"
 
 namespace aca {
 
@@ -35,19 +36,6 @@ constexpr int FB_KF = 3136, FB_N = 512;
 constexpr int FB_DW_TILES = (FB_KF / 64) * (FB_N / 64);   // 392
 constexpr int FB_LDH = FB_N / 2 + 8;  // LDS row of the dy3 operand blocks (bf16): one K half, 512 + 16 bytes
                                       // (rows 4 banks apart: conflict-free b128 fragment reads)
-
-struct FcBwdArgs {
-  const u16* dh;      // [B][512] bf16
-  const u16* W;       // Wfc [3136][512] bf16 (row-major shadow)
-  const u16* y3;      // [B][3136] bf16 (saved activations, ReLU outputs)
-  u16* dy3;           // [B][3136] bf16
-  float* dW;          // [3136][512] fp32
-  int B;
-  int n_dy;           // dy3 tiles: ceil(B / 32) x 98
-  uint64_t* stamps;   // diagnostics: per workgroup [entry, operands in, MFMAs done, stores issued]
-  float* sq;          // optional: per (dWfc tile, wave) sum of squares [392 x 4] (the finaliser's norm partials
-                      // then need no 6.4 MB re-read of dWfc)
-};
 
 __device__ __forceinline__ void fb_stamp(uint64_t* st, int slot) {
   if (st && threadIdx.x == 0) st[(size_t)blockIdx.x * 4 + slot] = __builtin_amdgcn_s_memrealtime();
@@ -205,12 +193,13 @@ __global__ void __launch_bounds__(FB_THREADS, 4) fc_bwd_kernel(FcBwdArgs a) {
 
 // dh [B][512], W = Wfc [3136][512], y3 [B][3136] bf16 -> dy3 [B][3136] bf16, dW [3136][512] fp32; 1 <= B <= 256,
 // every pointer 16-byte aligned, the row strides dense.
-extern "C" hipError_t aca_fc_bwd(const uint16_t* dh, const uint16_t* W, const uint16_t* y3, uint16_t* dy3, float* dW,
-                                 int B, float* sq, uint64_t* stamps, hipStream_t stream) {
+extern "C" hipError_t aca_fc_bwd(const aca::FcBwdArgs* args, hipStream_t stream) {
+  aca::FcBwdArgs a = *args;
+  const int B = a.B;
   if (B < 1 || B > aca::FB_MAXB) return hipErrorInvalidValue;
-  for (const void* p : {(const void*)dh, (const void*)W, (const void*)y3, (const void*)dy3, (const void*)dW})
+  for (const void* p : {(const void*)a.dh, (const void*)a.W, (const void*)a.y3, (const void*)a.dy3, (const void*)a.dW})
     if (!p || reinterpret_cast<uintptr_t>(p) % 16) return hipErrorInvalidValue;
-  aca::FcBwdArgs a{dh, W, y3, dy3, dW, B, ((B + 31) / 32) * (aca::FB_KF / 32), stamps, sq};
+  a.n_dy = ((B + 31) / 32) * (aca::FB_KF / 32);
   const int Bp = (B + 15) & ~15;
   const size_t lds = std::max((size_t)4 * Bp * 32 * 2, (size_t)2 * 32 * aca::FB_LDH * 2);
   aca::fc_bwd_kernel<<<aca::FB_DW_TILES + a.n_dy, aca::FB_THREADS, lds, stream>>>(a);

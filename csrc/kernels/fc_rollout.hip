@@ -17,17 +17,11 @@
 // Workgroup order is XCD-grouped: the 16 column blocks of a k chunk run on one XCD, so their shared X lines meet in
 // one L2; the same workgroup reads the same W fragments every launch (they stay in that XCD's L2 across steps).
 #include "common.h"
+#include "launch_api.h"
 
 namespace aca {
 
 typedef float fr_f32x16 __attribute__((ext_vector_type(16)));
-
-struct FcRolloutArgs {
-  const u16* X; int64_t ldx; int M;
-  const u16* Wf; int K, N;
-  float* P; int64_t pstride;
-  unsigned long long* stamps;   // diagnostics: per wave [entry, operands landed, MFMAs done, stores drained]
-};
 
 template <int KR, int W, int MT>
 __global__ void __launch_bounds__(64 * W) fc_rollout_kernel(FcRolloutArgs a) {
@@ -106,21 +100,20 @@ __global__ void __launch_bounds__(64 * W) fc_rollout_kernel(FcRolloutArgs a) {
 // variant: (KR, W) = 0: (2, 7) -> 14 planes, 1: (4, 7) -> 7 planes, 2: (1, 14) -> 14 planes, 3: (7, 4) -> 7 planes,
 // 4: (7, 2) -> 14 planes, 5: (2, 14) -> 7 planes, 6: (1, 7) -> 28 planes, 7: (7, 7) -> 4 planes, 8: (14, 1) -> 14
 // planes, 9: (7, 14) -> 2 planes. Returns the plane count through *S_out.
-extern "C" hipError_t aca_fc_rollout(const uint16_t* X, int64_t ldx, int M, const uint16_t* Wf, int K, int N,
-                                     float* P, int64_t pstride, int variant, int max_planes, int* S_out,
-                                     unsigned long long* stamps, int msplit, hipStream_t stream) {
+extern "C" hipError_t aca_fc_rollout(const aca::FcRolloutArgs* args, int variant, int max_planes, int* S_out,
+                                     int msplit, hipStream_t stream) {
   static const int cfg[10][2] = {{2, 7}, {4, 7}, {1, 14}, {7, 4}, {7, 2}, {2, 14}, {1, 7}, {7, 7}, {14, 1}, {7, 14}};
-  if (variant < 0 || variant > 9 || M < 1 || M > 128 || K % 16 || N % 32 || ldx % 8 ||
-      reinterpret_cast<uintptr_t>(X) % 16 || reinterpret_cast<uintptr_t>(Wf) % 16 || (N >> 5) % 8)
+  const aca::FcRolloutArgs& a = *args;
+  const int M = a.M, K = a.K, N = a.N;
+  if (variant < 0 || variant > 9 || M < 1 || M > 128 || K % 16 || N % 32 || a.ldx % 8 ||
+      reinterpret_cast<uintptr_t>(a.X) % 16 || reinterpret_cast<uintptr_t>(a.Wf) % 16 || (N >> 5) % 8)
     return hipErrorInvalidValue;
   const int kr = cfg[variant][0], w = cfg[variant][1];
   const int KB = K / 16;
   if (KB % (kr * w)) return hipErrorInvalidValue;
   const int S = KB / (kr * w);
-  if (S > max_planes || pstride < (int64_t)M * N) return hipErrorInvalidValue;
+  if (S > max_planes || a.pstride < (int64_t)M * N) return hipErrorInvalidValue;
   if (S_out) *S_out = S;
-  aca::FcRolloutArgs a{reinterpret_cast<const aca::u16*>(X), ldx, M, reinterpret_cast<const aca::u16*>(Wf), K, N, P,
-                       pstride, stamps};
   const int grid = S * (N >> 5);
   // 32-row blocks of X per wave (the fc's B fragments loaded once for all of them), or with msplit one block per
   // workgroup row (gridDim.y)

@@ -1,5 +1,6 @@
 // Host-side entry of the MFMA GEMM (kernel: gemm_impl.h; instantiations: gemm_plain.hip, gemm_conv.hip).
 #include "gemm_impl.h"
+#include "launch_api.h"
 
 namespace aca {
 hipError_t gemm_plain(const GemmParams& P, hipStream_t s);

@@ -25,7 +25,7 @@
 // Requirements (host-checked): plain bf16 operands, 16-byte aligned, lda / ldb % 8 == 0, K % 64 == 0 (splits take
 // ceil(K / 64 / splits) k-steps each, the last one the rest), the m/n-contiguous extents % 8 == 0.
 #include "common.h"
-#include "gemm_desc.h"
+#include "launch_api.h"
 
 namespace aca {
 

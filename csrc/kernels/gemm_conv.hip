@@ -2,8 +2,7 @@
 // input image; weight gradient: B gathered from the input image; data gradient: A gathered from the output gradient
 // as a transposed conv, B = the OHWI weight read transposed).
 #include "gemm_impl.h"
-
-extern "C" int aca_gemm_tile_dims(int tile, int* bm, int* bn);
+#include "launch_api.h"
 
 namespace aca {
 hipError_t gemm_conv(const GemmParams& P, hipStream_t s) {

@@ -5,10 +5,7 @@
 // tile configurations the autotuner picks for those products (up to two configurations per launch); any other
 // combination falls back to one launch per product (aca_gemm_group_run).
 #include "gemm_impl.h"
-
-extern "C" int aca_gemm_tile_dims(int tile, int* bm, int* bn);
-extern "C" hipError_t aca_gemm_run(const AcaGemmDesc* d, hipStream_t stream);
-extern "C" int aca_gemm_effective_splits(int K, int bk, int splits);
+#include "launch_api.h"
 
 namespace aca {
 

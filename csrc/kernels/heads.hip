@@ -6,6 +6,7 @@
 //   sum_i log N(a_i), sum_i (1/2 + 1/2 log 2pi + log sigma_i).
 // Oracles: ops/distributions.py (*_ref).
 #include "common.h"
+#include "launch_api.h"
 
 namespace aca {
 

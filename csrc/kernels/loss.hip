@@ -20,37 +20,9 @@
 // dz = the gradient of the head bias, written directly (the gradient slab is clean).
 #include "common.h"
 #include "cnn_head.h"
+#include "launch_api.h"
 
 namespace aca {
-
-struct LossArgs {
-  const float* logits; int64_t ldl;     // or mu for the gaussian head
-  const float* value; int64_t ldv;      // may be null (no critic term)
-  const int32_t* act_i;                 // categorical actions
-  const float* act_f;                   // gaussian actions [B, A]
-  const float* log_std;                 // gaussian
-  const float* logp_old;
-  const float* adv;
-  const float* ret;
-  const float* v_old;                   // may be null
-  const float* ent_coef;                // device scalar
-  const float* kl_coef;                 // device scalar
-  float vf_coef, ppo_clip, v_clip;
-  u16* dlogits; int64_t lddl;
-  u16* dvalue; int64_t lddv;
-  float* dlog_std;                      // gaussian: fp32 [A] (atomic add)
-  float* stats;
-  int B, A;
-  int gaussian;
-  // fused returns (A2C): rew/done [T, N], val [T+1, N]; ret/adv (global scratch [B]) are written then read back
-  int returns_mode;                     // 0: use ret/adv as given; 1: n-step (look-ahead L); 2: GAE(lambda)
-  const float* rew; const float* val; const uint8_t* dn;
-  int T, N, L;
-  float gamma, lam;
-  int norm_adv;
-  float* ret_w; float* adv_w;
-  float* dbias; int dbias_n;            // head bias gradient (A+1 columns: logits | value)
-};
 
 // threads of ac_loss_kernel: the categorical specialisations run 16 waves (a B = 4096 PPO minibatch is 4 row
 // iterations per thread, not 16 -- each iteration is a dependent memory round trip); the generic form (runtime A,
@@ -336,25 +308,6 @@ constexpr int HB_H = 512;
 constexpr int HB_WG = 8;                    // workgroups (64 hidden columns each)
 constexpr int HB_RPT = HB_MAXB / 64;        // row slots per thread in the head phase (8)
 
-struct HeadBwdArgs {
-  const float* z;            // [B, A1] logits | value
-  const int32_t* act;
-  const float* logp_old;
-  const float* ent_coef; const float* kl_coef;
-  float vf_coef;
-  const float* rew; const float* val; const uint8_t* dn;
-  int T, N, L, returns_mode, norm_adv;
-  float gamma, lam;
-  float* ret_w; float* adv_w;
-  const u16* h;              // [B, 512] bf16 (rollout activations)
-  const u16* Wh;             // [512, A1] bf16 shadow
-  u16* dh;                   // [B, 512] out
-  float* gWh; float* gbh; float* gbfc;
-  float* stats;
-  int B;
-  uint64_t* stamps;          // optional [HB_WG, 16] s_memrealtime phase stamps (diagnostics; null in production)
-};
-
 __device__ __forceinline__ void hb_stamp(const HeadBwdArgs& a, int slot) {
   if (a.stamps && threadIdx.x == 0) a.stamps[(size_t)blockIdx.x * 16 + slot] = __builtin_amdgcn_s_memrealtime();
 }
@@ -611,14 +564,6 @@ constexpr int AH_MAXB = 512;
 constexpr int AH_MAXN = 256;
 constexpr int AH_RPT = AH_MAXB / 64;         // row slots per thread in the head phase
 constexpr unsigned int AH_SPIN_LIMIT = 1u << 21;
-
-struct A2cHeadArgs {
-  HeadBwdArgs h;
-  const float* hpart; int S; int64_t plane_stride;   // last fc product (split-K planes) of s_T, or null: val holds V(s_T)
-  const float* bfc; const float* bh;
-  float* vboot;              // [N] = val + B (written in phase 0)
-  unsigned int* bar;         // [0] arrivals, [1] departures, [2] timeout flag
-};
 
 template <int AC>
 __global__ void __launch_bounds__(AH_THREADS) a2c_head_kernel(A2cHeadArgs args) {
@@ -940,14 +885,6 @@ __global__ void __launch_bounds__(AH_THREADS) a2c_head_kernel(A2cHeadArgs args) 
 constexpr int AE_THREADS = 256;
 constexpr int AE_MAXT = 64;
 
-struct A2cEnvArgs {
-  HeadBwdArgs h;
-  const float* hpart; int S; int64_t plane_stride;   // last fc product of s_T (split-K planes), or null: val[T] holds V
-  const float* bfc; const float* bh;
-  float* pWh; float* pbfc; float* pbh;               // planes [N][512 * A1], [N][512], [N][A1]
-  double* spart;                                     // [N][A2C_STATS] statistics rows
-};
-
 template <int AC>
 __global__ void __launch_bounds__(AE_THREADS) a2c_head_env_kernel(A2cEnvArgs args) {
   constexpr int A1 = AC + 1;
@@ -1150,17 +1087,12 @@ __global__ void __launch_bounds__(AE_THREADS) a2c_head_env_kernel(A2cEnvArgs arg
 
 }  // namespace aca
 
-extern "C" hipError_t aca_head_bwd(const float* z, const int32_t* act, const float* logp_old, const float* ent_coef,
-                                   const float* kl_coef, float vf_coef, const float* rew, const float* val,
-                                   const uint8_t* dn, int T, int N, int L, int returns_mode, int norm_adv, float gamma,
-                                   float lam, float* ret_w, float* adv_w, const uint16_t* h, const uint16_t* Wh,
-                                   uint16_t* dh, float* gWh, float* gbh, float* gbfc, float* stats, int A,
-                                   uint64_t* stamps, hipStream_t stream) {
-  const int B = T * N;
-  if (B < 1 || B > aca::HB_MAXB || N > 256 || A < 2 || A > 7 || (returns_mode != 1 && returns_mode != 2))
+extern "C" hipError_t aca_head_bwd(const aca::HeadBwdArgs* args, int A, hipStream_t stream) {
+  aca::HeadBwdArgs a = *args;
+  const int N = a.N, B = a.T * N;
+  if (B < 1 || B > aca::HB_MAXB || N > 256 || A < 2 || A > 7 || (a.returns_mode != 1 && a.returns_mode != 2))
     return hipErrorInvalidValue;
-  aca::HeadBwdArgs a{z, act, logp_old, ent_coef, kl_coef, vf_coef, rew, val, dn, T, N, L, returns_mode, norm_adv,
-                     gamma, lam, ret_w, adv_w, h, Wh, dh, gWh, gbh, gbfc, stats, B, stamps};
+  a.B = B;
   switch (A) {
 #define ACA_HB_CASE(n) \
   case n: aca::head_bwd_kernel<n><<<aca::HB_WG, aca::HB_THREADS, 0, stream>>>(a); break;
@@ -1170,23 +1102,18 @@ extern "C" hipError_t aca_head_bwd(const float* z, const int32_t* act, const flo
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_a2c_head(const float* z, const int32_t* act, const float* logp_old, const float* ent_coef,
-                                   const float* kl_coef, float vf_coef, const float* rew, float* val,
-                                   const uint8_t* dn, int T, int N, int L, int returns_mode, int norm_adv, float gamma,
-                                   float lam, float* ret_w, float* adv_w, const uint16_t* h, const uint16_t* Wh,
-                                   uint16_t* dh, float* gWh, float* gbh, float* gbfc, float* stats, int A,
-                                   const float* hpart, int S, int64_t plane_stride, const float* bfc, const float* bh,
-                                   unsigned int* bar, uint64_t* stamps, hipStream_t stream) {
-  const int B = T * N;
-  if (B < 1 || B > aca::AH_MAXB || N > aca::AH_MAXN || A < 2 || A > 7 || (returns_mode != 1 && returns_mode != 2))
+extern "C" hipError_t aca_a2c_head(const aca::A2cHeadArgs* args, int A, hipStream_t stream) {
+  aca::A2cHeadArgs a = *args;
+  const int B = a.h.T * a.h.N;
+  if (B < 1 || B > aca::AH_MAXB || a.h.N > aca::AH_MAXN || A < 2 || A > 7 ||
+      (a.h.returns_mode != 1 && a.h.returns_mode != 2))
     return hipErrorInvalidValue;
-  if (hpart && (S < 1 || S > aca::FC_MAX_PLANES || !bfc || !bh || !bar || reinterpret_cast<uintptr_t>(hpart) % 16 ||
-                reinterpret_cast<uintptr_t>(bfc) % 16 || plane_stride % 4))
+  if (a.hpart && (a.S < 1 || a.S > aca::FC_MAX_PLANES || !a.bfc || !a.bh || !a.bar ||
+                  reinterpret_cast<uintptr_t>(a.hpart) % 16 || reinterpret_cast<uintptr_t>(a.bfc) % 16 ||
+                  a.plane_stride % 4))
     return hipErrorInvalidValue;
-  aca::A2cHeadArgs a;
-  a.h = aca::HeadBwdArgs{z, act, logp_old, ent_coef, kl_coef, vf_coef, rew, val, dn, T, N, L, returns_mode, norm_adv,
-                         gamma, lam, ret_w, adv_w, h, Wh, dh, gWh, gbh, gbfc, stats, B, stamps};
-  a.hpart = hpart; a.S = S; a.plane_stride = plane_stride; a.bfc = bfc; a.bh = bh; a.vboot = val + B; a.bar = bar;
+  a.h.B = B;
+  a.vboot = const_cast<float*>(a.h.val) + B;   // val is the caller's writable [T + 1, N] buffer
   switch (A) {
 #define ACA_AH_CASE(n) \
   case n: aca::a2c_head_kernel<n><<<aca::AH_WG, aca::AH_THREADS, 0, stream>>>(a); break;
@@ -1196,26 +1123,17 @@ extern "C" hipError_t aca_a2c_head(const float* z, const int32_t* act, const flo
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_a2c_head_env(const float* z, const int32_t* act, const float* logp_old,
-                                       const float* ent_coef, const float* kl_coef, float vf_coef, const float* rew,
-                                       float* val, const uint8_t* dn, int T, int N, int L, int returns_mode,
-                                       float gamma, float lam, float* ret_w, float* adv_w, const uint16_t* h,
-                                       const uint16_t* Wh, uint16_t* dh, int A, const float* hpart, int S,
-                                       int64_t plane_stride, const float* bfc, const float* bh, float* pWh,
-                                       float* pbfc, float* pbh, double* spart, uint64_t* stamps,
-                                       hipStream_t stream) {
-  const int B = T * N;
-  if (T < 1 || T > aca::AE_MAXT || N < 1 || A < 2 || A > 7 || (returns_mode != 1 && returns_mode != 2) || !pWh ||
-      !pbfc || !pbh || !spart)
+extern "C" hipError_t aca_a2c_head_env(const aca::A2cEnvArgs* args, int A, hipStream_t stream) {
+  aca::A2cEnvArgs a = *args;
+  const int T = a.h.T, N = a.h.N;
+  if (T < 1 || T > aca::AE_MAXT || N < 1 || A < 2 || A > 7 || (a.h.returns_mode != 1 && a.h.returns_mode != 2) ||
+      !a.pWh || !a.pbfc || !a.pbh || !a.spart)
     return hipErrorInvalidValue;
-  if (hpart && (S < 1 || S > aca::FC_MAX_PLANES || !bfc || !bh || reinterpret_cast<uintptr_t>(hpart) % 16 ||
-                reinterpret_cast<uintptr_t>(bfc) % 16 || plane_stride % 4))
+  if (a.hpart && (a.S < 1 || a.S > aca::FC_MAX_PLANES || !a.bfc || !a.bh ||
+                  reinterpret_cast<uintptr_t>(a.hpart) % 16 || reinterpret_cast<uintptr_t>(a.bfc) % 16 ||
+                  a.plane_stride % 4))
     return hipErrorInvalidValue;
-  aca::A2cEnvArgs a;
-  a.h = aca::HeadBwdArgs{z, act, logp_old, ent_coef, kl_coef, vf_coef, rew, val, dn, T, N, L, returns_mode, 0,
-                         gamma, lam, ret_w, adv_w, h, Wh, dh, nullptr, nullptr, nullptr, nullptr, B, stamps};
-  a.hpart = hpart; a.S = S; a.plane_stride = plane_stride; a.bfc = bfc; a.bh = bh;
-  a.pWh = pWh; a.pbfc = pbfc; a.pbh = pbh; a.spart = spart;
+  a.h.B = T * N;
   switch (A) {
 #define ACA_AE_CASE(n) \
   case n: aca::a2c_head_env_kernel<n><<<N, aca::AE_THREADS, 0, stream>>>(a); break;
@@ -1225,26 +1143,13 @@ extern "C" hipError_t aca_a2c_head_env(const float* z, const int32_t* act, const
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_ac_loss(const float* logits, int64_t ldl, const float* value, int64_t ldv,
-                                  const int32_t* act_i, const float* act_f, const float* log_std,
-                                  const float* logp_old, const float* adv, const float* ret, const float* v_old,
-                                  const float* ent_coef, const float* kl_coef, float vf_coef, float ppo_clip,
-                                  float v_clip, uint16_t* dlogits, int64_t lddl, uint16_t* dvalue, int64_t lddv,
-                                  float* dlog_std, float* stats, int B, int A, int gaussian, int returns_mode,
-                                  const float* rew, const float* val, const uint8_t* dn, int T, int N, int L,
-                                  float gamma, float lam, int norm_adv, float* ret_w, float* adv_w, float* dbias,
-                                  int dbias_n, hipStream_t stream) {
-  if (A > 64 || dbias_n > aca::CAT_MAX + 1 || (!gaussian && A > aca::CAT_MAX)) return hipErrorInvalidValue;
-  if (returns_mode && (T * N != B || !rew || !val || !dn || !ret_w || !adv_w)) return hipErrorInvalidValue;
-  aca::LossArgs a;
-  a.logits = logits; a.ldl = ldl; a.value = value; a.ldv = ldv; a.act_i = act_i; a.act_f = act_f;
-  a.log_std = log_std; a.logp_old = logp_old; a.adv = adv; a.ret = ret; a.v_old = v_old; a.ent_coef = ent_coef;
-  a.kl_coef = kl_coef; a.vf_coef = vf_coef; a.ppo_clip = ppo_clip; a.v_clip = v_clip; a.dlogits = dlogits;
-  a.lddl = lddl; a.dvalue = dvalue; a.lddv = lddv; a.dlog_std = dlog_std; a.stats = stats; a.B = B; a.A = A;
-  a.gaussian = gaussian;
-  a.returns_mode = returns_mode; a.rew = rew; a.val = val; a.dn = dn; a.T = T; a.N = N; a.L = L; a.gamma = gamma;
-  a.lam = lam; a.norm_adv = norm_adv; a.ret_w = ret_w; a.adv_w = adv_w; a.dbias = dbias; a.dbias_n = dbias_n;
-  if (!gaussian && A >= 2 && A <= 19) {
+extern "C" hipError_t aca_ac_loss(const aca::LossArgs* args, hipStream_t stream) {
+  const aca::LossArgs& a = *args;
+  const int A = a.A;
+  if (A > 64 || a.dbias_n > aca::CAT_MAX + 1 || (!a.gaussian && A > aca::CAT_MAX)) return hipErrorInvalidValue;
+  if (a.returns_mode && (a.T * a.N != a.B || !a.rew || !a.val || !a.dn || !a.ret_w || !a.adv_w))
+    return hipErrorInvalidValue;
+  if (!a.gaussian && A >= 2 && A <= 19) {
     switch (A) {
 #define ACA_LOSS_CASE(n) \
   case n: aca::ac_loss_kernel<n><<<1, aca::loss_threads<n>(), 0, stream>>>(a); break;

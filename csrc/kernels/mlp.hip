@@ -36,7 +36,7 @@
 #include <type_traits>
 
 #include "common.h"
-#include "mlp_desc.h"
+#include "launch_api.h"
 
 namespace aca {
 

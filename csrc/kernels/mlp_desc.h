@@ -1,5 +1,6 @@
 // Descriptors shared by the MLP engine kernels (mlp.hip) and the torch-op bindings (bindings.cpp): plain C types
-// only, so both hipcc and g++ compile this header.
+// only, so both hipcc and g++ compile this header. Both sides get it, and the launchers' declarations, through
+// launch_api.h.
 #pragma once
 #include <stdint.h>
 

@@ -11,6 +11,7 @@
 // workgroup sums the same slots in the same order, so no in-kernel cross-workgroup hand-off (and no L2 write-back
 // fence) is needed for the global norm.
 #include "common.h"
+#include "launch_api.h"
 
 namespace aca {
 
@@ -1025,7 +1026,14 @@ extern "C" hipError_t aca_grad_finalize(const int64_t* jobs, int njobs, float* p
                                         hipStream_t stream) {
   if (njobs < 1 || njobs > SUMSQ_PARTS) return hipErrorInvalidValue;
   if (spart && (sN < 1 || sB < 1 || !ent_coef || !kl_coef || !stats)) return hipErrorInvalidValue;
-  const StatsDuty sd{spart, sN, sB, ent_coef, kl_coef, stats, sppo};
+  StatsDuty sd{};
+  sd.part = spart;
+  sd.N = sN;
+  sd.B = sB;
+  sd.ent_coef = ent_coef;
+  sd.kl_coef = kl_coef;
+  sd.stats = stats;
+  sd.ppo = sppo;
   grad_finalize_kernel<<<njobs + (spart ? 1 : 0), OPT_THREADS, 0, stream>>>(jobs, njobs, partial, sd);
   return hipGetLastError();
 }
@@ -1068,33 +1076,49 @@ static bool opt_aligned(const float* p, const float* g, const float* m, const fl
             reinterpret_cast<uintptr_t>(v)) % 16 || reinterpret_cast<uintptr_t>(shadow) % 8);
 }
 
-extern "C" hipError_t aca_adam_step(float* p, float* g, float* m, float* v, size_t n, const float* lr,
-                                    float* t, const float* gnorm_parts, float* gnorm_out, uint16_t* shadow, float b1, float b2, float eps,
-                                    float clip, float max_norm, unsigned int* ticket, int zero_grad,
-                                    float gmul, float norm_mul, const int64_t* trans, const uint16_t* g16,
-                                    hipStream_t stream) {
-  if (n == 0) return hipSuccess;
-  if (!opt_aligned(p, g, m, v, shadow) || reinterpret_cast<uintptr_t>(g16) % 8) return hipErrorInvalidValue;
-  OptSeg S{p, g, m, v, n, lr, t, gnorm_parts, gnorm_out, shadow, clip, max_norm, gmul, norm_mul, ticket, opt_grid(n),
-           0, {}};
-  S.g16 = g16;
-  if (!ticket || !t) return hipErrorInvalidValue;
-  if (!opt_load_trans(S, trans)) return hipErrorInvalidValue;
-  launch_opt<true>(S, b1, b2, eps, zero_grad, stream);
+// the fields of a single-segment launch that Adam and RMSprop share
+static OptSeg opt_step_seg(const aca::OptStepArgs& a) {
+  OptSeg S{};
+  S.p = a.p;
+  S.g = a.g;
+  S.v = a.v;
+  S.n = a.n;
+  S.lr = a.lr;
+  S.parts = a.gnorm_parts;
+  S.gnorm_out = a.gnorm_out;
+  S.shadow = a.shadow;
+  S.clip = a.clip;
+  S.max_norm = a.max_norm;
+  S.gmul = a.gmul;
+  S.norm_mul = a.norm_mul;
+  S.nblocks = opt_grid(a.n);
+  S.g16 = a.g16;
+  return S;
+}
+
+extern "C" hipError_t aca_adam_step(const aca::OptStepArgs* args, hipStream_t stream) {
+  const aca::OptStepArgs& a = *args;
+  if (a.n == 0) return hipSuccess;
+  if (!opt_aligned(a.p, a.g, a.m, a.v, a.shadow) || reinterpret_cast<uintptr_t>(a.g16) % 8)
+    return hipErrorInvalidValue;
+  OptSeg S = opt_step_seg(a);
+  S.m = a.m;
+  S.t = a.t;
+  S.ticket = a.ticket;
+  if (!a.ticket || !a.t) return hipErrorInvalidValue;
+  if (!opt_load_trans(S, a.trans)) return hipErrorInvalidValue;
+  launch_opt<true>(S, a.b1, a.b2, a.eps, a.zero_grad, stream);
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_rmsprop_step(float* p, float* g, float* v, size_t n, const float* lr,
-                                       const float* gnorm_parts, float* gnorm_out, uint16_t* shadow, float alpha, float eps, float clip,
-                                       float max_norm, int zero_grad, float gmul, float norm_mul,
-                                       const int64_t* trans, const uint16_t* g16, hipStream_t stream) {
-  if (n == 0) return hipSuccess;
-  if (!opt_aligned(p, g, v, v, shadow) || reinterpret_cast<uintptr_t>(g16) % 8) return hipErrorInvalidValue;
-  OptSeg S{p, g, nullptr, v, n, lr, nullptr, gnorm_parts, gnorm_out, shadow, clip, max_norm, gmul, norm_mul, nullptr,
-           opt_grid(n), 0, {}};
-  S.g16 = g16;
-  if (!opt_load_trans(S, trans)) return hipErrorInvalidValue;
-  launch_opt<false>(S, 0.f, alpha, eps, zero_grad, stream);
+extern "C" hipError_t aca_rmsprop_step(const aca::OptStepArgs* args, hipStream_t stream) {
+  const aca::OptStepArgs& a = *args;   // m, t, ticket, b1 unused; b2 = alpha
+  if (a.n == 0) return hipSuccess;
+  if (!opt_aligned(a.p, a.g, a.v, a.v, a.shadow) || reinterpret_cast<uintptr_t>(a.g16) % 8)
+    return hipErrorInvalidValue;
+  OptSeg S = opt_step_seg(a);
+  if (!opt_load_trans(S, a.trans)) return hipErrorInvalidValue;
+  launch_opt<false>(S, 0.f, a.b2, a.eps, a.zero_grad, stream);
   return hipGetLastError();
 }
 

@@ -3,6 +3,7 @@
 // `fp contract(off)`: it must round exactly like the PyTorch oracle (envs/atari.py) in every including file.
 #pragma once
 #include "common.h"
+#include "env_args.h"   // PongIO
 
 namespace aca {
 
@@ -33,12 +34,6 @@ __device__ __forceinline__ float clampf(float x, float lo, float hi) { return fm
 __device__ __forceinline__ void stamp_if(uint64_t* st, int slot, bool who) {
   if (st && who) st[(size_t)blockIdx.x * 16 + slot] = __builtin_amdgcn_s_memrealtime();
 }
-
-struct PongIO {
-  float* state; int32_t* tsteps; int64_t* tglob; float* ep_ret; float* ep_stats; const int64_t* env_ids;
-  const uint8_t* prev; uint8_t* out; float* reward; uint8_t* done_out; uint8_t* trunc_out;
-  uint32_t seed; int max_steps; int k;
-};
 
 // Result of advancing env `e` by one agent step (4 physics sub-steps) -- computed from global state without writing
 // anything, so the fused rollout kernel can evaluate all three paddle directions while the policy is still sampling.

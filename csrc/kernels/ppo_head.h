@@ -1,4 +1,5 @@
-// Argument block of the large-batch learner head launch (ppo_head.hip), shared with csrc/bindings.cpp.
+// Argument block of the large-batch learner head launch (ppo_head.hip), shared with csrc/bindings.cpp: both sides
+// get it, and the launcher's declaration, through launch_api.h.
 #pragma once
 #include <stdint.h>
 

@@ -20,7 +20,7 @@
 // workgroup (agent-scope release / acquire ticket, common.h last_block_arrival) sums the records in a fixed order
 // (common.h grid_records_sum).
 #include "common.h"
-#include "ppo_head.h"
+#include "launch_api.h"
 
 namespace aca {
 

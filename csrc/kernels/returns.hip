@@ -8,6 +8,7 @@
 // * moments: sum, sum of squares of x and y and cross term (EV correlation Basic_AC/util.py:4-12).
 // Oracles: ops/returns.py, utils/stats.py.
 #include "common.h"
+#include "launch_api.h"
 
 namespace aca {
 
@@ -245,21 +246,6 @@ __global__ void __launch_bounds__(256) seg_stats_kernel(const float* __restrict_
 constexpr int RS_THREADS = 256;
 constexpr int RS_MOM = 7;
 constexpr int RS_KREG = 8;   // chunks up to this many steps stay in registers between the passes
-
-struct RetScanArgs {
-  const float* r;
-  const float* v;
-  const uint8_t* d;
-  float* ret;
-  float* adv;
-  double* gz;            // [T, N] (truncated n-step windows only)
-  double* part;          // [gridDim.x, 8]
-  unsigned int* ticket;  // zero before the first launch; self-cleaning
-  double* mom;           // [8]: count, then the RS_MOM sums
-  float* ev_out;         // EV(ret, V[:T]) or null
-  int T, N, E, CH, K, mode, L, norm;
-  float gamma, lam, eps;
-};
 
 __global__ void __launch_bounds__(RS_THREADS) returns_scan_kernel(RetScanArgs a) {
   __shared__ double s_a[RS_THREADS], s_c[RS_THREADS];
@@ -570,14 +556,11 @@ extern "C" void aca_returns_scan_geometry(int T, int N, int* E, int* CH, int* K,
   *blocks = (N + *E - 1) / *E;
 }
 
-extern "C" hipError_t aca_returns_scan(const float* r, const float* v, const uint8_t* d, float* ret, float* adv,
-                                       double* gz, double* part, unsigned int* ticket, double* mom, float* ev_out,
-                                       int T, int N, int mode, int L, int norm, float gamma, float lam, float eps,
-                                       hipStream_t stream) {
-  if (T <= 0 || N <= 0) return hipSuccess;
-  aca::RetScanArgs a{r, v, d, ret, adv, gz, part, ticket, mom, ev_out, T, N, 0, 0, 0, mode, L, norm, gamma, lam, eps};
+extern "C" hipError_t aca_returns_scan(const aca::RetScanArgs* args, hipStream_t stream) {
+  aca::RetScanArgs a = *args;
+  if (a.T <= 0 || a.N <= 0) return hipSuccess;
   int blocks;
-  aca_returns_scan_geometry(T, N, &a.E, &a.CH, &a.K, &blocks);
+  aca_returns_scan_geometry(a.T, a.N, &a.E, &a.CH, &a.K, &blocks);
   aca::returns_scan_kernel<<<blocks, aca::RS_THREADS, 0, stream>>>(a);
   return hipGetLastError();
 }
@@ -599,19 +582,15 @@ extern "C" hipError_t aca_ev_multi(const float* x, const float* y, float* out, i
   return hipGetLastError();
 }
 
-extern "C" hipError_t aca_mb_gather(const uint8_t* obs, int64_t R, const int* act, const float* logp, const float* adv,
-                                    const float* ret, const float* v, uint8_t* o_obs, int* o_act, float* o_logp,
-                                    float* o_adv, float* o_ret, float* o_v, int mb, int n, uint32_t seed,
-                                    int64_t* uc, int ep, int off, const double* mom, float eps,
-                                    unsigned int* bump_ticket, int64_t* o_idx, hipStream_t stream) {
-  if (mb <= 0) return hipSuccess;
-  if (!o_idx && !o_obs) return hipErrorInvalidValue;
-  if (o_idx)
-    aca::mb_gather_kernel<<<(mb + 255) / 256, 256, 0, stream>>>(obs, R, act, logp, adv, ret, v, nullptr, o_act,
-                                                                 o_logp, o_adv, o_ret, o_v, n, seed, uc, ep, off, mom,
-                                                                 eps, bump_ticket, o_idx, mb);
-  else
-    aca::mb_gather_kernel<<<mb, 256, 0, stream>>>(obs, R, act, logp, adv, ret, v, o_obs, o_act, o_logp, o_adv, o_ret,
-                                                  o_v, n, seed, uc, ep, off, mom, eps, bump_ticket, nullptr, mb);
+extern "C" hipError_t aca_mb_gather(const aca::MbGatherArgs* args, hipStream_t stream) {
+  const aca::MbGatherArgs& a = *args;
+  if (a.mb <= 0) return hipSuccess;
+  if (!a.o_idx && !a.o_obs) return hipErrorInvalidValue;
+  // index mode: one thread per minibatch row and no observation copy; else one workgroup per row
+  const int grid = a.o_idx ? (a.mb + 255) / 256 : a.mb;
+  aca::mb_gather_kernel<<<grid, 256, 0, stream>>>(a.obs, a.R, a.act, a.logp, a.adv, a.ret, a.v,
+                                                  a.o_idx ? nullptr : a.o_obs, a.o_act, a.o_logp, a.o_adv, a.o_ret,
+                                                  a.o_v, a.n, a.seed, a.uc, a.ep, a.off, a.mom, a.eps, a.bump_ticket,
+                                                  a.o_idx, a.mb);
   return hipGetLastError();
 }

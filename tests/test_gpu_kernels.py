@@ -158,6 +158,39 @@ def test_env_bank_matches_oracle(cuda, env_id):
     assert torch.allclose(cpu.ep_stats, gpu.ep_stats.cpu(), rtol=1e-4, atol=1e-3)
 
 
+@pytest.mark.parametrize("env_id", ["CartPole-v1", "Pendulum-v0", "HalfCheetahShape-v0"])
+def test_env_bank_final_obs_matches_oracle(cuda, env_id):
+    """The optional terminal-observation output of the vector-observation env kernels (final_out: the stack holding
+    the transition's new frame before any auto-reset) == the torch oracle's, on two envs with a 3-step time limit so
+    that every third step resets; same oracle and tolerances as test_env_bank_matches_oracle."""
+    from actor_critic_algs_on_tensorflow_amd import envs as E
+    N = 2
+    gpu = E.make(env_id, N, device=cuda, seed=5, max_episode_steps=3)
+    cpu = E.make(env_id, N, device="cpu", seed=5, max_episode_steps=3)
+    assert gpu.native_final_obs
+    for bank in (gpu, cpu):
+        bank.keep_final_obs = True
+        bank.reset()
+    gpu.state.copy_(cpu.state)
+    gpu.obs.copy_(cpu.obs)
+    g = torch.Generator().manual_seed(1)
+    resets = 0
+    for t in range(7):
+        a = cpu.sample_actions(generator=g)
+        prev_c, prev_g = cpu.obs.clone(), gpu.obs.clone()
+        oc, rc, dc, _ = cpu.step(a, prev_obs=prev_c, obs_out=cpu.obs)
+        og, rg, dg, _ = gpu.step(a.to(cuda), prev_obs=prev_g, obs_out=gpu.obs)
+        assert torch.equal(dc, dg.cpu()), (env_id, t)
+        assert torch.allclose(cpu.final_obs, gpu.final_obs.cpu(), rtol=1e-4, atol=1e-4), (env_id, t)
+        assert torch.allclose(oc, og.cpu(), rtol=1e-4, atol=1e-4), (env_id, t)
+        if bool(dc.all()):   # the terminal stack is the pre-reset observation, not the reset one that follows
+            resets += 1
+            assert not torch.equal(gpu.final_obs, og), (env_id, t)
+        gpu.state.copy_(cpu.state)
+        gpu.obs.copy_(cpu.obs)
+    assert resets >= 2
+
+
 # ------------------------------------------------------------------------------------------------------ heads / returns
 def test_categorical_and_gaussian_heads(cuda):
     from actor_critic_algs_on_tensorflow_amd.ops import distributions as D
@@ -230,6 +263,31 @@ def test_fused_optimizers(cuda, name, clip, max_norm):
     assert torch.allclose(b[1].float(), b[0], rtol=1e-2, atol=1e-3)
     if name == "adam":
         assert a[2] == b[2] == 5.0
+
+
+@pytest.mark.parametrize("name", ["adam", "rmsprop"])
+def test_fused_optimizers_read_bf16_gradient(cuda, name):
+    """The optional bf16 gradient operand (g16: the all-reduced bf16 comm buffer of data-parallel runs, read in place
+    of the fp32 slab by the update and by its global-norm partials) against the torch oracle reading the same bf16
+    values; test_fused_optimizers' tolerances. n spans several workgroups and is not a multiple of the vector width."""
+    from actor_critic_algs_on_tensorflow_amd.ops.optim import FlatParams, make_optimizer
+    n = 4099
+    p0 = torch.randn(n)
+    res = {}
+    for dev in ("cpu", cuda):
+        p = torch.nn.Parameter(p0.clone())
+        flat = FlatParams({"shared": [p]}, torch.device(dev))
+        opt = make_optimizer(name, flat, "shared", 1e-3, None, 0.5)
+        g16 = torch.zeros(flat.numel, dtype=torch.bfloat16, device=dev)
+        opt.bind_grad16(g16)
+        g = torch.Generator().manual_seed(4)
+        for _ in range(3):
+            g16[:n].copy_((torch.randn(n, generator=g) * 0.3).to(dev))
+            flat.grad.fill_(float("nan"))   # must not be read
+            opt.step()
+        res[str(dev)] = flat.data.cpu()[:n]
+    assert torch.isfinite(res[str(cuda)]).all()
+    assert torch.allclose(res["cpu"], res[str(cuda)], rtol=1e-5, atol=1e-6)
 
 
 # ------------------------------------------------------------------------------------------------------ loss
