@@ -295,12 +295,16 @@ class ActorCriticTrainer:
     @torch.no_grad()
     def _collect_mlp(self):
         """MuJoCo-shaped bank: ONE persistent launch for the whole rollout + one critic launch (ops/mlp.py
-        ``rollout_linear``). Otherwise one launch per step for the policy (both towers + sampling) and one for the
+        ``rollout_linear``), with ``bootstrap_on_timeout`` plus one critic launch over the terminal-observation slots
+        and one fix-up launch. Otherwise one launch per step for the policy (both towers + sampling) and one for the
         env bank."""
         st, env, eng = self.storage, self.env, self.mlp
         boot = self.cfg.bootstrap_on_timeout
-        if self.cfg.fused_rollout and eng.supports_fused_rollout(env) and not boot:
-            eng.rollout_linear(env, st, KEY_ENV_BITS, self.policy_seed)
+        if self.cfg.fused_rollout and eng.supports_fused_rollout(env):
+            # time-limit bootstrap: the launch keeps the truncated steps' terminal observations in compact slots; one
+            # critic launch over the slots and one fix-up launch put gamma * V(terminal observation) into the rewards
+            eng.rollout_linear(env, st, KEY_ENV_BITS, self.policy_seed,
+                               boot=self._timeout_boot_ws() if boot else None)
             return
         if boot and getattr(self, "_final_obs", None) is None:
             self._final_obs = torch.zeros((st.T,) + tuple(st.obs.shape[1:]), dtype=st.obs.dtype, device=self.device)
@@ -318,6 +322,22 @@ class ActorCriticTrainer:
             eng.value(self._final_obs.view(st.T * st.N, -1), self._final_v)
             st.rewards.addcmul_(self._final_v.view(st.T, st.N), st.truncated.to(torch.float32),
                                 value=self.cfg.gamma)
+
+    def _timeout_boot_ws(self):
+        """The fused rollout's bootstrap workspace (``ops/mlp.py`` TimeoutBootWorkspace), built on first use and
+        rebuilt when the rollout geometry or the bank's time limit changed. Allocation happens outside graph capture
+        (the warm-up collect builds it); a captured graph holds its addresses and its slot count."""
+        from ..ops.mlp import TimeoutBootWorkspace
+        st, env, eng = self.storage, self.env, self.mlp
+        ws = getattr(self, "_boot_ws", None)
+        if ws is None or not ws.fits(st.T, st.N, eng.D, env.max_episode_steps):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("bootstrap_on_timeout: the fused rollout's terminal-observation workspace must be "
+                                   "built before graph capture (n_steps, num_envs or env.max_episode_steps changed "
+                                   "after the warm-up collect)")
+            ws = self._boot_ws = TimeoutBootWorkspace(st.T, st.N, eng.D, env.max_episode_steps, self.cfg.gamma,
+                                                      self.device)
+        return ws
 
     def _reuse_acts(self):
         """A2C takes one gradient step at the parameters that acted, so the rollout's forward activations ARE the

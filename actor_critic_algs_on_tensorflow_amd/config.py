@@ -86,6 +86,9 @@ class TrainConfig:
     look_ahead: int | None = None     # n-step truncation L (reference: 40); None = whole rollout
     gae_lambda: float = 0.95
     norm_adv: bool = False
+    # a time-limit cut stays an episode boundary, and its step's reward gets gamma * V(terminal observation). Runs on
+    # the torch engine and the native MLP engine (classic banks per step; the MuJoCo-shaped bank inside the
+    # one-launch fused rollout), not on the native CNN engine
     bootstrap_on_timeout: bool = False
     # -- losses ------------------------------------------------------------------------------------------------
     ent_coef: float = 0.01            # reference "gamma" (Basic_AC/policies.py:38)

@@ -16,7 +16,10 @@ per 16 rows with its activations in LDS, on f32 MFMA:
 * :meth:`MLPEngine.rollout_linear` -- the whole T-step rollout of the MuJoCo-shaped bank in ONE persistent launch
   (actor on 4x4x1 MFMA tiles + sampling + env dynamics + frame stack per 4-env workgroup, ``mlp_rollout_kernel``) followed by ONE
   batched critic launch over all ``(T+1) N`` observations (the rollout's Session.run-per-step loop of
-  ``Basic_AC/run_AC.py:82-107``).
+  ``Basic_AC/run_AC.py:82-107``). With a :class:`TimeoutBootWorkspace` the same launch also keeps the terminal
+  observation of every step the time limit cut, in :func:`timeout_slots` compact slots per env; one more critic launch
+  over those ``N S`` stacks and one fix-up launch (``ops/returns.py`` ``timeout_bootstrap_``) then add
+  ``gamma V(terminal observation)`` to the truncated steps' rewards (``TrainConfig.bootstrap_on_timeout``).
 
 Weights are read in place from the fp32 parameter slab (TF ``[in, out]`` kernels, so checkpoints need no
 transposes) and gradients are written straight into the gradient slab.
@@ -67,6 +70,33 @@ def frag_f(W):
 def frag_g(W):
     """Data-gradient fragment copy of a [K][N] weight (common.h mlp_frag_g): [ngp2(K) tiles][ngp2(N) groups][64][4]."""
     return frag_f(W.t())
+
+
+def timeout_slots(T, max_steps):
+    """Terminal-observation slots per env of a T-step fused rollout: an env enters with ``t0 < max_steps`` steps of
+    its episode behind it and is truncated ``floor((t0 + T) / max_steps) <= ceil(T / max_steps)`` times."""
+    T, max_steps = int(T), int(max_steps)
+    if T < 1 or max_steps < 1:
+        raise ValueError(f"timeout_slots needs T >= 1 and max_steps >= 1, got {T}, {max_steps}")
+    return (T + max_steps - 1) // max_steps
+
+
+class TimeoutBootWorkspace:
+    """Device buffers of the fused rollout's time-limit bootstrap (:meth:`MLPEngine.rollout_linear`): ``final_obs``
+    ``[N, S, D]``, the terminal observation stacks; ``final_step`` int32 ``[N, S]``, the step of every slot (``-1``:
+    unused; the rollout launch writes every entry); ``final_v`` ``[N, S]``, the critic's values of the slots; ``gamma``,
+    the trainer's discount. ``S = timeout_slots(T, max_steps)``. Create outside any graph capture."""
+
+    def __init__(self, T, N, D, max_steps, gamma, device):
+        self.T, self.N, self.D, self.max_steps = int(T), int(N), int(D), int(max_steps)
+        self.S = timeout_slots(T, max_steps)
+        self.gamma = float(gamma)
+        self.final_obs = torch.zeros(self.N, self.S, self.D, dtype=torch.float32, device=device)
+        self.final_step = torch.full((self.N, self.S), -1, dtype=torch.int32, device=device)
+        self.final_v = torch.zeros(self.N, self.S, dtype=torch.float32, device=device)
+
+    def fits(self, T, N, D, max_steps):
+        return (self.T, self.N, self.D, self.max_steps) == (int(T), int(N), int(D), int(max_steps))
 
 
 class MLPEngine:
@@ -311,15 +341,28 @@ class MLPEngine:
     def rollout_weights_in_lds(self):
         return self.rollout_lds_bytes(True) <= self.ROLLOUT_MAX_LDS
 
-    def rollout_linear(self, env, st, key_shift, seed, stamps=None):
+    def rollout_linear(self, env, st, key_shift, seed, stamps=None, boot=None):
         """T steps of policy + env for the whole bank in one launch, then V(s) of all (T+1) N observations in one
         critic launch. Equal to T x (:meth:`policy_step` + ``env.step``) + :meth:`value` up to the actor's fp32
-        summation order (4x4x1 tiles with the K range split over waves vs 16x16x4 tiles): same RNG keys and resets."""
+        summation order (4x4x1 tiles with the K range split over waves vs 16x16x4 tiles): same RNG keys and resets.
+
+        ``boot`` (a :class:`TimeoutBootWorkspace` for this ``T``, ``N``, ``D`` and ``env.max_episode_steps``): the
+        time-limit bootstrap. The rollout launch keeps the terminal observation of every truncated step in the
+        workspace's slots, one more critic launch values the ``N S`` slots and one fix-up launch adds
+        ``gamma V(terminal observation)`` to those steps' rewards (unused slots are valued but never read)."""
         T, N = st.T, env.num_envs
         desc, _ = self.desc(None)
         wlds = self.rollout_weights_in_lds()
+        if boot is not None and not boot.fits(T, N, self.D, env.max_episode_steps):
+            raise ValueError("rollout_linear: the bootstrap workspace was built for another rollout geometry")
         _native.require().mlp_rollout(desc, self.rollout_lds_bytes(wlds), st.obs, st.actions, st.logp, st.entropy,
                                       st.rewards, st.dones, st.truncated, self.log_std, self.ac_scale, key_shift, seed,
                                       env.state, env.t, env.tg, env.ep_ret, env.ep_stats, env.env_ids, env.A, env.B,
-                                      env.seed, env.max_episode_steps, env.frame_stack, wlds, stamps)
+                                      env.seed, env.max_episode_steps, env.frame_stack, wlds, stamps,
+                                      None if boot is None else boot.final_obs,
+                                      None if boot is None else boot.final_step)
         self.value(st.obs.view((T + 1) * N, -1), st.values.view(-1))
+        if boot is not None:
+            from .returns import timeout_bootstrap_
+            self.value(boot.final_obs.view(N * boot.S, -1), boot.final_v.view(-1))
+            timeout_bootstrap_(st.rewards, boot.final_step, boot.final_v, boot.gamma)

@@ -143,6 +143,33 @@ def normalize_advantages(adv, eps=1e-8):
     return (a - a.mean()) / (eps + a.std(unbiased=False))
 
 
+def timeout_bootstrap_ref_(rewards, final_step, v_final, gamma):
+    """PyTorch oracle of :func:`timeout_bootstrap_` (any device): fp32 multiply, then add."""
+    T, N = rewards.shape
+    step = final_step.reshape(N, -1).long()
+    env = torch.arange(N, device=rewards.device)[:, None].expand_as(step)
+    used = step >= 0
+    boot = torch.tensor(gamma, dtype=torch.float32, device=rewards.device) * v_final.reshape(N, -1).float()
+    # every (step, env) sits in at most one slot: a plain indexed add
+    rewards[step[used], env[used]] += boot[used].to(rewards.dtype)
+    return rewards
+
+
+def timeout_bootstrap_(rewards, final_step, v_final, gamma):
+    """Time-limit bootstrap of a rollout whose terminal observations sit in compact slots: in place,
+    ``rewards[final_step[i, s], i] += gamma * v_final[i, s]`` for every slot with ``final_step[i, s] >= 0``.
+
+    ``rewards`` fp32 ``[T, N]``; ``final_step`` int32 ``[N, S]``, the step at which env ``i`` was truncated for the
+    ``s``-th time in this rollout or ``-1`` (unused: its ``v_final`` is never read); ``v_final`` fp32 ``[N, S]``, the
+    critic's value of the terminal observation of every slot. One HIP launch on GPU
+    (``timeout_bootstrap_kernel`` in ``csrc/kernels/returns.hip``)."""
+    if _native.use_native(rewards):
+        N = rewards.shape[1]
+        _native.require().timeout_bootstrap(rewards, final_step.view(N, -1), v_final.view(N, -1), float(gamma))
+        return rewards
+    return timeout_bootstrap_ref_(rewards, final_step, v_final, gamma)
+
+
 class ScanWorkspace:
     """Device workspace of :func:`returns_scan` / the many-workgroup EV: per-workgroup fp64 partial moments, the
     self-cleaning last-arriver ticket, the fp64 totals ``mom`` (``[count, sum adv, sum adv^2, sum ret, sum ret^2,

@@ -604,6 +604,25 @@ void returns_scan(Tensor r, Tensor v, Tensor d, Tensor ret, Tensor adv, int64_t 
   check(aca_returns_scan(&a, cur_stream(r)), "returns_scan");
 }
 
+// Time-limit bootstrap of a fused rollout: rewards[final_step[i, s], i] += gamma * v_final[i, s] for every used slot.
+void timeout_bootstrap(Tensor rewards, Tensor final_step, Tensor v_final, double gamma) {
+  need(rewards, at::kFloat, "rewards");
+  need(final_step, at::kInt, "final_step");
+  need(v_final, at::kFloat, "v_final");
+  TORCH_CHECK(rewards.dim() == 2 && final_step.dim() == 2 && final_step.size(0) == rewards.size(1) &&
+                  v_final.numel() == final_step.numel(),
+              "timeout_bootstrap: rewards [T, N], final_step [N, S], v_final [N, S]");
+  aca::TimeoutBootArgs a{};
+  a.reward = ptr<float>(rewards);
+  a.final_step = ptr<int32_t>(final_step);
+  a.v_final = ptr<float>(v_final);
+  a.T = (int)rewards.size(0);
+  a.N = (int)rewards.size(1);
+  a.S = (int)final_step.size(1);
+  a.gamma = (float)gamma;
+  check(aca_timeout_bootstrap(&a, cur_stream(rewards)), "timeout_bootstrap");
+}
+
 // conv1 weight gradient as P partial planes [P][32][256] (conv_wgrad.hip): obs uint8 [B, 4, 84, 84], dy1 bf16
 // [B * 400, 32]; plane g holds samples [g B / P, (g + 1) B / P).
 // obs_idx (optional int64 [B]): sample b's frames are row obs_idx[b] of obs (a PPO minibatch gathered by index)
@@ -1138,7 +1157,7 @@ void mlp_rollout(Tensor desc, int64_t lds, Tensor obs, Tensor act, Tensor logp, 
                  Tensor done, Tensor trunc, Tensor log_std, Tensor ac_scale, int64_t key_shift, int64_t policy_seed,
                  Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, Tensor lin_A,
                  Tensor lin_B, int64_t env_seed, int64_t max_steps, int64_t k, bool wlds,
-                 c10::optional<Tensor> stamps) {
+                 c10::optional<Tensor> stamps, c10::optional<Tensor> final_obs, c10::optional<Tensor> final_step) {
   need(desc, at::kLong, "desc");
   TORCH_CHECK(desc.numel() * 8 >= (int64_t)sizeof(aca::MlpTower), "mlp_rollout: desc too small");
   need(obs, at::kFloat, "obs");
@@ -1191,6 +1210,20 @@ void mlp_rollout(Tensor desc, int64_t lds, Tensor obs, Tensor act, Tensor logp, 
   a.max_steps = (int)max_steps;
   a.wlds = wlds ? 1 : 0;
   a.stamps = reinterpret_cast<int64_t*>(stamps_ptr(stamps, 16));   // [16 steps][8 phases] + per-wave layer stamps + flag
+  // time-limit bootstrap: terminal observation slots [N, S, D] and their steps [N, S] (the launcher checks S)
+  TORCH_CHECK(has(final_obs) == has(final_step), "mlp_rollout: final_obs and final_step go together");
+  if (has(final_obs)) {
+    need(*final_obs, at::kFloat, "final_obs");
+    need(*final_step, at::kInt, "final_step");
+    TORCH_CHECK(final_obs->dim() == 3 && final_obs->size(0) == N && final_obs->size(1) >= 1 &&
+                    final_obs->size(2) == D, "mlp_rollout: final_obs must be [N, S, D]");
+    const int64_t S = final_obs->size(1);
+    TORCH_CHECK(final_step->dim() == 2 && final_step->size(0) == N && final_step->size(1) == S,
+                "mlp_rollout: final_step must be [N, S]");
+    a.final_obs = ptr<float>(*final_obs);
+    a.final_step = ptr<int32_t>(*final_step);
+    a.S = (int)S;
+  }
   check(aca_mlp_rollout(&a, (size_t)lds, cur_stream(obs)), "mlp_rollout");
 }
 
@@ -2029,7 +2062,9 @@ TORCH_LIBRARY(acamd, m) {
   m.def("mlp_rollout(Tensor desc, int lds, Tensor obs, Tensor act, Tensor logp, Tensor ent, Tensor reward, "
         "Tensor done, Tensor truncated, Tensor log_std, Tensor ac_scale, int key_shift, int policy_seed, "
         "Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, Tensor lin_A, "
-        "Tensor lin_B, int env_seed, int max_steps, int k, bool wlds, Tensor? stamps=None) -> ()");
+        "Tensor lin_B, int env_seed, int max_steps, int k, bool wlds, Tensor? stamps=None, Tensor? final_obs=None, "
+        "Tensor? final_step=None) -> ()");
+  m.def("timeout_bootstrap(Tensor rewards, Tensor final_step, Tensor v_final, float gamma) -> ()");
   m.def("gemm(Tensor A, int lda, bool a_k, Tensor B, int ldb, bool b_k, Tensor C, int ldc, int out_mode, int M, "
         "int N, int K, float alpha, Tensor? bias, bool relu, Tensor? mask, int ldm, Tensor? colsum, int colsum_mod, "
         "int tile, int bk, int splits, Tensor? ws, Tensor? tickets, int[] ga, float ga_scale, int[] gb, "
@@ -2115,6 +2150,7 @@ TORCH_LIBRARY_IMPL(acamd, CUDA, m) {
   m.impl("mlp_tshadow", &mlp_tshadow);
   m.impl("mlp_wgrad", &mlp_wgrad);
   m.impl("mlp_rollout", &mlp_rollout);
+  m.impl("timeout_bootstrap", &timeout_bootstrap);
   m.impl("mlp_epoch_gather", &mlp_epoch_gather);
   m.impl("gemm", &gemm);
   m.impl("cnn_trunk_fwd", &cnn_trunk_fwd);

@@ -82,6 +82,7 @@ int aca_ev_multi_blocks(int n);
 hipError_t aca_ev_multi(const float* x, const float* y, float* out, int n, double* part, unsigned int* ticket,
                         hipStream_t stream);
 hipError_t aca_mb_gather(const aca::MbGatherArgs* a, hipStream_t stream);
+hipError_t aca_timeout_bootstrap(const aca::TimeoutBootArgs* a, hipStream_t stream);
 
 // ---- loss and learner heads (loss.hip, ppo_head.hip); A = number of actions
 hipError_t aca_ac_loss(const aca::LossArgs* a, hipStream_t stream);

@@ -1519,12 +1519,15 @@ __device__ __forceinline__ void roll_layer_epilogue(const float* __restrict__ re
 // parameters and env ids are staged as well.
 // KP0: the padded observation width (32 / 64: frame stacks of 1 / 2-3); the actor is the reference's 128-128-64-A
 // (ops/mlp.py supports_fused_rollout)
-template <int KP0>
+// BOOT: the time-limit bootstrap's instantiation also keeps the terminal (pre-reset) observation stack of every
+// truncated step in a.final_obs / a.final_step; its extra stores exist in this instantiation only
+template <int KP0, bool BOOT>
 __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // 16-byte base: the b128 LDS reads stay aligned
   __shared__ int64_t s_tg[ROLL_RB];
   __shared__ int64_t s_ids[ROLL_RB];
   __shared__ int s_t[ROLL_RB];
+  __shared__ int s_ne[ROLL_RB];   // BOOT: terminal-observation slots the env has used so far
   __shared__ float s_er[ROLL_RB];
   __shared__ float s_ls[MLP_MAXA], s_sc[MLP_MAXA];
   __shared__ float s_hl[ROLL_RB * MLP_MAXA];
@@ -1561,6 +1564,7 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
     s_ids[tid] = live ? a.env_ids[row0 + tid] : 0;
     s_t[tid] = live ? a.t[row0 + tid] : 0;
     s_er[tid] = live ? a.ep_ret[row0 + tid] : 0.f;
+    if constexpr (BOOT) s_ne[tid] = 0;
   }
   __syncthreads();
   // diagnostics: 100 MHz stamps at phase boundaries (workgroup 0, wave 0 after the barrier), steps 0..15
@@ -1747,6 +1751,31 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
         const float er = s_er[e] + rew;
         ret = er;
         len = (float)t;
+        if constexpr (BOOT) {
+          // terminal observation of a truncated step (linear_step_kernel's final_out): the stack shifted by one frame
+          // with the pre-reset row y appended, into the env's next free slot
+          if (trunc) {   // rare (once per max_steps steps): the other steps read and write nothing here
+            const int ne = s_ne[e];
+            if (ne < a.S) {
+              if (r < LIN_OBS) {
+                // (kept small on purpose -- no unrolling, no frame loop at all for k = 1: this rare block must not
+                // cost the actor layers registers)
+                const int k = a.k;
+                float* fo = a.final_obs + ((size_t)i * a.S + ne) * D;
+                if constexpr (KP0 > 32) {   // frame stacks of 2-3
+                  const float* pv = Xc + e * ld0;
+#pragma nounroll
+                  for (int f = 0; f < k - 1; ++f) fo[f * LIN_OBS + r] = pv[(f + 1) * LIN_OBS + r];
+                }
+                fo[(k - 1) * LIN_OBS + r] = y;
+              }
+              if (owner) {   // (the group's lanes have read s_ne[e]: same wave, program order)
+                a.final_step[(size_t)i * a.S + ne] = step;
+                s_ne[e] = ne + 1;
+              }
+            }
+          }
+        }
         if (done && r < LIN_OBS) y = lin_reset(uniform01(a.env_seed, id, st, 100 + r));
         if (r < LIN_OBS) {
           s[r] = y;
@@ -1783,6 +1812,8 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
     a.tg[row0 + tid] = s_tg[tid];
     a.t[row0 + tid] = s_t[tid];
     a.ep_ret[row0 + tid] = s_er[tid];
+    if constexpr (BOOT)   // unused slots: the table is valid after every launch without a host-side clear
+      for (int s = s_ne[tid]; s < a.S; ++s) a.final_step[(size_t)(row0 + tid) * a.S + s] = -1;
   }
 }
 
@@ -1849,18 +1880,30 @@ extern "C" hipError_t aca_mlp_rollout(const RolloutArgs* a, size_t lds, hipStrea
   if (a->N <= 0 || a->T <= 0) return hipSuccess;
   if (!a->tw || a->head != 2 || a->A != LIN_ACT || a->k < 1 || a->k > 3 || a->D != LIN_OBS * a->k || !a->wlds)
     return hipErrorInvalidValue;
+  // terminal observations: an env that enters with t < max_steps truncates at most ceil(T / max_steps) times
+  const bool boot = a->final_obs != nullptr;
+  if (boot && (!a->final_step || a->max_steps < 1 ||
+               (int64_t)a->S * a->max_steps < (int64_t)a->T))   // S < ceil(T / max_steps)
+    return hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_rollout_kernel<32>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, ROLLOUT_MAX_LDS) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_rollout_kernel<64>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, ROLLOUT_MAX_LDS) != hipSuccess)
-      return hipErrorInvalidValue;
+    const void* ks[4] = {reinterpret_cast<const void*>(&mlp_rollout_kernel<32, false>),
+                         reinterpret_cast<const void*>(&mlp_rollout_kernel<64, false>),
+                         reinterpret_cast<const void*>(&mlp_rollout_kernel<32, true>),
+                         reinterpret_cast<const void*>(&mlp_rollout_kernel<64, true>)};
+    for (const void* k : ks)
+      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, ROLLOUT_MAX_LDS) != hipSuccess)
+        return hipErrorInvalidValue;
     attr = true;
   }
   if (lds > ROLLOUT_MAX_LDS) return hipErrorInvalidValue;
   const dim3 grid((a->N + ROLL_RB - 1) / ROLL_RB);
-  if (a->k == 1) mlp_rollout_kernel<32><<<grid, MLP_THREADS, lds, stream>>>(*a);
-  else mlp_rollout_kernel<64><<<grid, MLP_THREADS, lds, stream>>>(*a);
+  if (boot) {
+    if (a->k == 1) mlp_rollout_kernel<32, true><<<grid, MLP_THREADS, lds, stream>>>(*a);
+    else mlp_rollout_kernel<64, true><<<grid, MLP_THREADS, lds, stream>>>(*a);
+  } else {
+    if (a->k == 1) mlp_rollout_kernel<32, false><<<grid, MLP_THREADS, lds, stream>>>(*a);
+    else mlp_rollout_kernel<64, false><<<grid, MLP_THREADS, lds, stream>>>(*a);
+  }
   return hipGetLastError();
 }

@@ -91,6 +91,11 @@ struct RolloutArgs {
   uint32_t env_seed; int max_steps;
   int wlds;                   // actor weights staged in LDS (host decides from the LDS budget)
   int64_t* stamps;            // optional diagnostics: s_memrealtime per phase of the first 16 steps (workgroup 0)
+  // optional (time-limit bootstrap): the pre-reset observation stack of every truncated step, in S compact slots per
+  // env (an env truncates at most ceil(T / max_steps) times per rollout), and the step each slot belongs to
+  float* final_obs;           // [N][S][D]; null: not kept
+  int32_t* final_step;        // [N][S]: step of slot (i, s), -1 = unused (every slot is written by every launch)
+  int S;
 };
 
 }  // namespace aca

@@ -499,7 +499,33 @@ __global__ void __launch_bounds__(RS_THREADS) ev_multi_kernel(const float* __res
   }
 }
 
+// Time-limit bootstrap of a fused rollout (mlp.hip mlp_rollout_kernel keeps the terminal observations of truncated
+// steps in S slots per env): one thread per slot adds gamma * V(terminal observation) to its step's reward. Every
+// (step, env) sits in at most one slot, so plain stores; an unused slot (-1) reads nothing. Multiply, then add (no
+// fma), like the per-step path's arithmetic. Oracle: ops/returns.py timeout_bootstrap_ref_.
+__device__ __forceinline__ float boot_reward(float r, float gamma, float v) {
+#pragma clang fp contract(off)
+  const float b = gamma * v;
+  return r + b;
+}
+
+__global__ void __launch_bounds__(256) timeout_bootstrap_kernel(TimeoutBootArgs a) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= a.N * a.S) return;
+  const int step = a.final_step[idx];
+  if (step < 0 || step >= a.T) return;
+  const size_t o = (size_t)step * a.N + idx / a.S;
+  a.reward[o] = boot_reward(a.reward[o], a.gamma, a.v_final[idx]);
+}
+
 }  // namespace aca
+
+extern "C" hipError_t aca_timeout_bootstrap(const aca::TimeoutBootArgs* a, hipStream_t stream) {
+  if (a->N <= 0 || a->S <= 0 || a->T <= 0) return hipSuccess;
+  if (!a->reward || !a->final_step || !a->v_final || (int64_t)a->N * a->S > INT32_MAX) return hipErrorInvalidValue;
+  aca::timeout_bootstrap_kernel<<<(a->N * a->S + 255) / 256, 256, 0, stream>>>(*a);
+  return hipGetLastError();
+}
 
 extern "C" hipError_t aca_ev(const float* x, const float* y, float* out, int n, hipStream_t stream) {
   aca::ev_kernel<<<1, 1024, 0, stream>>>(x, y, out, n);

@@ -35,4 +35,14 @@ struct MbGatherArgs {
   int64_t* o_idx;                  // index mode: the source row of every minibatch row [mb]
 };
 
+// operands of aca_timeout_bootstrap: the time-limit bootstrap of a rollout whose terminal observations sit in S
+// compact slots per env (mlp_desc.h RolloutArgs final_obs / final_step)
+struct TimeoutBootArgs {
+  float* reward;              // [T, N], in place: reward[step, i] += gamma * v_final[i, s] for every used slot
+  const int32_t* final_step;  // [N, S]: the step of slot (i, s), or -1 (unused: its v_final is never read)
+  const float* v_final;       // [N, S]: V(terminal observation) of every slot
+  int T, N, S;
+  float gamma;
+};
+
 }  // namespace aca
