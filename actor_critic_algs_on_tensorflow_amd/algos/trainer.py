@@ -136,6 +136,8 @@ class ActorCriticTrainer:
         self.model = (model if model is not None else
                       build_model(self.env, cfg.model, cfg.model_variant, seed=cfg.seed)).to(self.device)
         self.flat = FlatParams(self.model.param_groups(), self.device)
+        if cfg.norm_obs:
+            self._check_norm_obs()
         if dp is not None:
             dp.broadcast_params(self.flat)
             if cfg.grad_bucket_dtype == "bf16" and dp.compress is None:
@@ -196,6 +198,18 @@ class ActorCriticTrainer:
         if cfg.bootstrap_on_timeout:
             self.env.keep_final_obs = True   # the torch env step keeps the pre-reset observation (envs/base.py)
         self.env.reset(out=self.storage.obs[0])
+        # running observation normalisation (ops/obs_norm.py): storage and the env bank keep RAW observations; the
+        # towers normalise where they read their input (native MLP engine: in-kernel), and the learner reads the
+        # plane `prepare` writes once per update. Everything is allocated here, outside graph capture.
+        self.obs_norm = None
+        if cfg.norm_obs:
+            from ..ops.obs_norm import ObsNormalizer
+            D = int(self.env.obs_shape[0])
+            self.obs_norm = ObsNormalizer(D, cfg.obs_clip, 1e-8, self.device)
+            self._obs_plane = torch.zeros(T * N, D, dtype=torch.float32, device=self.device)
+            self.obs_norm.reserve(T * N)
+            if self.mlp is not None:
+                self.mlp.obs_norm = self.obs_norm
         dev = self.device
         self.ent_coef = torch.tensor(cfg.ent_coef, device=dev)
         self.kl_coef = torch.tensor(cfg.kl_coef, device=dev)
@@ -232,6 +246,35 @@ class ActorCriticTrainer:
                                            self._summary_scopes(), self.flat)
         self.timer = PhaseTimer(self.device, enabled=cfg.trace)
         self._fault = parse_fault(cfg.fault_inject)
+
+    def _check_norm_obs(self):
+        """``norm_obs`` covers fp32 vector observations in front of the MLP towers (a2c / ppo)."""
+        from ..models.policy import CNNActorCritic
+        if isinstance(self.model, CNNActorCritic):
+            raise ValueError("norm_obs=True with a CNN model: its frames are already scaled by 1/255 in-kernel; "
+                             "observation normalisation is for the MLP models")
+        if self.cfg.algo not in ("a2c", "ppo"):
+            raise ValueError(f"norm_obs=True with algo={self.cfg.algo!r}: the reference-parity trainers (a3c, "
+                             "basic_ac) keep the reference's raw observations; use a2c or ppo")
+        if len(self.env.obs_shape) != 1 or self.env.obs_dtype != torch.float32:
+            raise ValueError("norm_obs=True needs fp32 vector observations")
+
+    def _nobs(self, obs):
+        """Torch engine: what a tower reads for the raw observations ``obs``."""
+        return obs if self.obs_norm is None else self.obs_norm.apply(obs)
+
+    def _prepare_obs(self):
+        """After the rollout: the learner's normalised plane and the batch statistics of ``obs[0:T]`` (``obs[T]`` is
+        the next rollout's ``obs[0]``), both with the tables that acted."""
+        if self.obs_norm is not None:
+            st = self.storage
+            self.obs_norm.prepare(st.flat("obs"), self._obs_plane, st.T * st.N)
+
+    def _merge_obs(self):
+        """End of the update: the rollout's statistics enter the state; the new tables first act in the next rollout.
+        Under DP every rank all-reduces its batch vector first (one small collective per update)."""
+        if self.obs_norm is not None:
+            self.obs_norm.merge(self.dp, self._comm)
 
     def _want_native(self):
         """The hand-written HIP engine runs the CNN family on GPU (``engine="auto"|"native"``)."""
@@ -276,7 +319,7 @@ class ActorCriticTrainer:
         st, env, model = self.storage, self.env, self.model
         for t in range(st.T):
             obs_t = st.obs[t]
-            pi, v = model(obs_t)
+            pi, v = model(self._nobs(obs_t))
             a, logp, ent = model.sample(pi, self._keys(), self.policy_seed)
             st.actions[t].copy_(a.view_as(st.actions[t]))
             st.logp[t].copy_(logp)
@@ -288,9 +331,9 @@ class ActorCriticTrainer:
                 # a time-limit cut stays an episode boundary (done = 1: nothing leaks into the next episode, whose
                 # reset observation already sits in obs[t+1]); the truncated step's reward gets gamma * V(terminal
                 # observation) -- the observation the auto-reset overwrote, kept by the bank in final_obs
-                vf = model.value(env.final_obs)
+                vf = model.value(self._nobs(env.final_obs))
                 st.rewards[t].add_(self.cfg.gamma * vf * st.truncated[t].to(vf.dtype))
-        st.values[st.T].copy_(model.value(st.obs[st.T]))
+        st.values[st.T].copy_(model.value(self._nobs(st.obs[st.T])))
 
     @torch.no_grad()
     def _collect_mlp(self):
@@ -676,6 +719,8 @@ class ActorCriticTrainer:
             return self._learn_native_update(ret, adv)
         cfg, st = self.cfg, self.storage
         obs, actions, logp_old = st.flat("obs"), st.flat("actions"), st.flat("logp")
+        if self.obs_norm is not None:
+            obs = self._obs_plane   # = apply(obs) with this update's tables (_prepare_obs)
         v_old = st.flat("values")
         adv = self._pre_learn_stats(ret, adv, v_old)
         if cfg.algo == "ppo":
@@ -783,6 +828,9 @@ class ActorCriticTrainer:
         adv = self._pre_learn_stats(ret, adv, v_old)
         adv, ret = adv.contiguous(), ret.contiguous()
         B = obs.shape[0]
+        # observation normaliser: the train launches read the plane written once per update (_prepare_obs); the
+        # evaluate launch of the KL rule below keeps the raw rows and normalises in-kernel
+        lobs = self._obs_plane if self.obs_norm is not None else obs
         if cfg.algo == "ppo":
             mb = B // cfg.ppo_minibatches
             uc = self.update_counter.view(1)
@@ -790,11 +838,11 @@ class ActorCriticTrainer:
             # step ticket, the counters advance once after the loop
             offsets = self.cfg.engine_opts.adam_step_offsets
             self._t_offs_used = 0
-            g = self._epoch_buffers(obs, actions, B)
+            g = self._epoch_buffers(lobs, actions, B)
             for ep in range(cfg.ppo_epochs):
                 # the epoch's rows in minibatch order (the keyed permutation, one gather launch): the train launches
                 # read contiguous rows, with no index or permutation round trip ahead of their input tiles
-                _native.require().mlp_epoch_gather(obs, actions, logp_old, adv, ret, v_old, g["obs"], g["act"],
+                _native.require().mlp_epoch_gather(lobs, actions, logp_old, adv, ret, v_old, g["obs"], g["act"],
                                                    g["logp"], g["adv"], g["ret"], g["v"], uc, ep, self.policy_seed)
                 for k in range(cfg.ppo_minibatches):
                     last = ep == cfg.ppo_epochs - 1 and k == cfg.ppo_minibatches - 1
@@ -808,7 +856,7 @@ class ActorCriticTrainer:
                 assert self._t_offs_used == cfg.ppo_epochs * cfg.ppo_minibatches
                 self._group_step.advance(self._t_offs_used)
         else:
-            self._mlp_step(eng, B, None, obs, actions, logp_old, adv, ret, v_old)
+            self._mlp_step(eng, B, None, lobs, actions, logp_old, adv, ret, v_old)
             self.update_counter += 1
         if self.lr_ctrl is not None or cfg.kl_coef > 0:
             if not hasattr(self, "_eval_buf"):
@@ -1041,10 +1089,12 @@ class ActorCriticTrainer:
     def update_body(self):
         with self.timer.phase("rollout"):
             self.collect()
+            self._prepare_obs()
         with self.timer.phase("returns"):
             ret, adv = self.compute_returns()
         with self.timer.phase("learn"):
             self.learn(ret, adv)
+        self._merge_obs()
         self.storage.roll_over()
 
     def _post_body(self):

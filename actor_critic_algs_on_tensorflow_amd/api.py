@@ -102,6 +102,7 @@ class Agent:
         self._ctr = 0
         self.engine_kind = engine
         self._eng = None
+        self.obs_norm = None   # frozen ops/obs_norm.py ObsNormalizer of a norm_obs checkpoint (from_checkpoint)
 
     def _engine(self):
         """Lazily builds the native engine over the model's parameters (None on CPU / engine="torch")."""
@@ -119,6 +120,7 @@ class Agent:
         elif isinstance(self.model, MLPActorCritic) and self.model.actor.ac_dim <= 16:
             from .ops.mlp import MLPEngine
             self._eng = ("mlp", MLPEngine(self.model, flat), flat)
+            self._eng[1].obs_norm = self.obs_norm   # the launches normalise their input tiles
         elif self.engine_kind == "native":
             raise ValueError("no native engine for this model")
         return self._eng
@@ -168,6 +170,11 @@ class Agent:
         ckpt.load_model(agent.model, t, v if v != "generic" else "basic", strict=True)
         agent.model.to(device)
         agent.device = torch.device(device)
+        sd = ckpt.obs_norm_state(t)
+        if sd is not None:   # a norm_obs checkpoint: act / value normalise with its statistics, frozen
+            from .ops.obs_norm import ObsNormalizer
+            agent.obs_norm = ObsNormalizer(sd["mean"].numel(), float(sd["clip"]), device=agent.device)
+            agent.obs_norm.load_state_dict(sd).freeze()
         return agent
 
     @torch.no_grad()
@@ -186,6 +193,8 @@ class Agent:
             a, logp, ent = res
         else:
             keys = torch.arange(N, dtype=torch.int64, device=self.device) + (ctr << 20)
+            if self.obs_norm is not None:
+                o = self.obs_norm.apply(o)
             a, logp, ent, _ = self.model.act(o, keys=keys, seed=self.seed, deterministic=deterministic)
         out = (a.cpu().numpy(), logp.cpu().numpy(), ent.cpu().numpy())
         return tuple(x[0] for x in out) if single else out
@@ -199,6 +208,8 @@ class Agent:
         o = torch.as_tensor(np.asarray(obs)).to(self.device)
         if o.dim() == self._obs_rank():
             o = o.unsqueeze(0)
+        if self.obs_norm is not None:
+            o = self.obs_norm.apply(o)
         return self.model.value(o).cpu().numpy()
 
 

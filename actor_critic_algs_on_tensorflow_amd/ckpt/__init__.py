@@ -16,8 +16,9 @@ This module writes and reads the same files through the C++ codec (:mod:`.codec`
   Kernels are stored ``[in, out]`` in both frameworks, so no transposes happen.
 * any other model (the Atari CNN): ``acamd/<module path>`` names.
 * native resume state (not in the reference, which cannot resume -- SURVEY §5.4) goes under ``_acamd/...`` keys:
-  optimiser moments/step/lr per group, iteration and env-step counters, env-bank state. TF ignores unknown keys
-  only if they are not requested, so reference tooling can still restore the model variables.
+  optimiser moments/step/lr per group, iteration and env-step counters, env-bank state, and -- for a ``norm_obs``
+  trainer -- the observation normaliser as fp64 tensors ``_acamd/obs_norm/{count,mean,m2,clip}``. TF ignores unknown
+  keys only if they are not requested, so reference tooling can still restore the model variables.
 
 A ``checkpoint`` state file (``model_checkpoint_path: "..."``) is written next to the bundles and the newest
 ``keep`` checkpoints are retained (``max_to_keep=3`` in the reference).
@@ -243,11 +244,30 @@ def save_trainer(trainer, path=None):
     tensors["_acamd/update_counter"] = trainer.update_counter
     tensors["_acamd/ent_coef"] = trainer.ent_coef
     tensors["_acamd/kl_coef"] = trainer.kl_coef
+    norm = getattr(trainer, "obs_norm", None)
+    if norm is not None:   # numpy float64: tensors would be stored as fp32 (_to_np)
+        for k, v in norm.state_dict().items():
+            tensors[OBS_NORM_PREFIX + k] = v.numpy().astype(np.float64)
     save_tensors(path, tensors)
     directory = os.path.dirname(path) or "."
     kept = _prune(directory, os.path.basename(path).rsplit("-", 1)[0], cfg.keep_checkpoints)
     _write_state_file(directory, path, kept or [path])
     return path
+
+
+OBS_NORM_PREFIX = "_acamd/obs_norm/"
+
+
+def obs_norm_state(tensors):
+    """The observation normaliser's state in a bundle (``{count, mean, m2, clip}`` as fp64 tensors), or None when the
+    bundle was written without ``norm_obs``."""
+    keys = [OBS_NORM_PREFIX + k for k in ("count", "mean", "m2", "clip")]
+    have = [k for k in keys if k in tensors]
+    if not have:
+        return None
+    if len(have) != len(keys):
+        raise KeyError(f"checkpoint lacks {sorted(set(keys) - set(have))}")
+    return {k[len(OBS_NORM_PREFIX):]: torch.as_tensor(np.array(tensors[k], dtype=np.float64)) for k in keys}
 
 
 def _assign(dst, arr):
@@ -283,6 +303,14 @@ def load_trainer(trainer, path):
         trainer.mlp.sync_shadow()
     for g, opt in trainer.opts.items():
         _load_opt_state(trainer, opt, g, t, path)
+    norm = getattr(trainer, "obs_norm", None)
+    if norm is not None:
+        sd = obs_norm_state(t)
+        if sd is None:
+            raise KeyError(f"checkpoint {path} lacks the observation normaliser tensors "
+                           f"{[OBS_NORM_PREFIX + k for k in ('count', 'mean', 'm2', 'clip')]} that a norm_obs=True "
+                           "trainer restores (it was written with norm_obs=False)")
+        norm.load_state_dict(sd)
     if "_acamd/iteration" in t:
         trainer.iteration = int(t["_acamd/iteration"])
         trainer.env_steps = int(t["_acamd/env_steps"])
@@ -311,4 +339,4 @@ def detect_variant(names):
 
 
 __all__ = ["codec", "save_trainer", "load_trainer", "save_tensors", "load_tensors", "load_model",
-           "reference_tensors", "model_tensors", "latest_checkpoint", "detect_variant"]
+           "reference_tensors", "model_tensors", "latest_checkpoint", "detect_variant", "obs_norm_state"]

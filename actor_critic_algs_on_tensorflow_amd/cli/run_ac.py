@@ -32,6 +32,8 @@ def build_parser():
     p.add_argument("--num_envs", default=None, type=int)
     p.add_argument("--metrics", default=None, help="JSONL metrics sidecar path")
     p.add_argument("--quiet", action="store_true")
+    p.add_argument("--norm-obs", action="store_true",
+                   help="running observation normalisation (TrainConfig.norm_obs; --algo a2c|ppo, MLP models)")
     return p
 
 
@@ -49,6 +51,8 @@ def main(argv=None):
         kw["device"] = a.device
     if a.num_envs:
         kw["num_envs"] = a.num_envs
+    if a.norm_obs:
+        kw["norm_obs"] = True
     cfg = preset(name, **kw)
     res = train(cfg)
     print("done: %d iterations, %d env steps, %.1f env-steps/s" % (res.iterations, res.env_steps,

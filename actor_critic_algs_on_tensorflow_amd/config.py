@@ -90,6 +90,11 @@ class TrainConfig:
     # the torch engine and the native MLP engine (classic banks per step; the MuJoCo-shaped bank inside the
     # one-launch fused rollout), not on the native CNN engine
     bootstrap_on_timeout: bool = False
+    # running per-feature mean / variance of the raw vector observations, applied in front of both MLP towers as
+    # clip((obs - mean) / sqrt(var + 1e-8), +-obs_clip) (ops/obs_norm.py). The tables are frozen for the whole of an
+    # update; its rollout's observations are merged after its learner. MLP models under a2c / ppo only
+    norm_obs: bool = False
+    obs_clip: float = 10.0
     # -- losses ------------------------------------------------------------------------------------------------
     ent_coef: float = 0.01            # reference "gamma" (Basic_AC/policies.py:38)
     kl_coef: float = 0.0              # reference "beta" (squared log-prob drift proxy)
@@ -163,6 +168,15 @@ class TrainConfig:
                              "only the critic would decay; pick one")
         if not isinstance(self.engine_opts, EngineOpts):
             self.engine_opts = EngineOpts(**dict(self.engine_opts or {}))
+        if self.norm_obs:
+            if self.algo in ("a3c", "basic_ac"):
+                raise ValueError(f"TrainConfig.norm_obs=True with algo={self.algo!r}: the reference-parity trainers "
+                                 "keep the reference's raw observations; use a2c or ppo")
+            if self.model == "cnn":
+                raise ValueError("TrainConfig.norm_obs=True with model='cnn': its frames are already scaled by 1/255 "
+                                 "in-kernel; observation normalisation is for the MLP models")
+            if not self.obs_clip > 0:
+                raise ValueError(f"TrainConfig.obs_clip={self.obs_clip}: must be > 0")
         if self.look_ahead is not None and int(self.look_ahead) < 1:
             raise ValueError(f"TrainConfig.look_ahead={self.look_ahead}: must be >= 1 (None = the whole rollout)")
 

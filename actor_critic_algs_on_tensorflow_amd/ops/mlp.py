@@ -161,6 +161,10 @@ class MLPEngine:
         self.n_weights = sum(l.in_features * l.out_features for tw in self.towers for l in tw)
         # reference tower shapes: the train launches take the SPEC path (every weight fragment preloaded, mlp.hip)
         self.spec = True
+        # optional running observation normaliser (ops/obs_norm.py ObsNormalizer): when attached, policy_step, value,
+        # evaluate and rollout_linear take RAW observations and normalise them as their input tiles are written;
+        # train reads whatever it is given (the trainer feeds it the pre-normalised plane)
+        self.obs_norm = None
         self.sync_shadow()
 
     def frag_copies(self):
@@ -235,13 +239,14 @@ class MLPEngine:
         desc, _ = self.desc(desc_B)
         obs2 = obs.reshape(obs.shape[0], -1)
         puc, pep, poff, pn, pseed = perm if perm is not None else (None, 0, 0, 0, 0)
+        tables, nclip = self.obs_norm.kernel_args() if (self.obs_norm is not None and mode != 2) else (None, 0.0)
         ops.mlp_fwd(desc, tw_base, ntw, mode, self.lds_bytes(mode, tw_base, ntw), obs2, idx, puc, pep, poff, pn,
                     pseed, B, self.head, self.A,
                     self.log_std, self.ac_scale, tg, env_ids, key_shift, seed, act_out, logp_out, ent_out, v_out,
                     act_in, logp_old, adv, ret, v_old, ent_coef, kl_coef, float(vf_coef), float(ppo_clip),
                     float(v_clip or 0.0), bool(ppo), self.g_log_std if mode == 2 else None,
                     self.mstats if mode == 2 else None, self._mpart(B) if mode == 2 else None, stamps,
-                    self._hdescs[desc_B] if (mode == 2 and self.spec) else None)
+                    self._hdescs[desc_B] if (mode == 2 and self.spec) else None, tables, nclip)
 
     # ------------------------------------------------------------------------------------------- API
     def policy_step(self, obs, act_out, logp_out, ent_out, v_out, tg, env_ids, key_shift, seed):
@@ -326,6 +331,7 @@ class MLPEngine:
                 and [l.out_features for l in self.towers[0]] == [128, 128, 64, LIN_ACT])   # mlp_rollout_kernel shapes
 
     ROLLOUT_MAX_LDS = 150 * 1024
+    ROLLOUT_NORM_LDS = 2 * 1024   # static LDS of the NORM instantiations (tables + normalised tile; mlp.hip)
     ROLL_RB = 4   # envs per rollout workgroup (mlp.hip ROLL_RB: 4x4x1 MFMA tiles)
 
     def rollout_lds_bytes(self, wlds):
@@ -339,7 +345,8 @@ class MLPEngine:
         return 4 * n
 
     def rollout_weights_in_lds(self):
-        return self.rollout_lds_bytes(True) <= self.ROLLOUT_MAX_LDS
+        cap = self.ROLLOUT_MAX_LDS - (self.ROLLOUT_NORM_LDS if self.obs_norm is not None else 0)
+        return self.rollout_lds_bytes(True) <= cap
 
     def rollout_linear(self, env, st, key_shift, seed, stamps=None, boot=None):
         """T steps of policy + env for the whole bank in one launch, then V(s) of all (T+1) N observations in one
@@ -347,7 +354,8 @@ class MLPEngine:
         summation order (4x4x1 tiles with the K range split over waves vs 16x16x4 tiles): same RNG keys and resets.
 
         ``boot`` (a :class:`TimeoutBootWorkspace` for this ``T``, ``N``, ``D`` and ``env.max_episode_steps``): the
-        time-limit bootstrap. The rollout launch keeps the terminal observation of every truncated step in the
+        time-limit bootstrap (with an observation normaliser attached the slots hold raw stacks, normalised by the
+        critic launch that values them). The rollout launch keeps the terminal observation of every truncated step in the
         workspace's slots, one more critic launch values the ``N S`` slots and one fix-up launch adds
         ``gamma V(terminal observation)`` to those steps' rewards (unused slots are valued but never read)."""
         T, N = st.T, env.num_envs
@@ -355,12 +363,15 @@ class MLPEngine:
         wlds = self.rollout_weights_in_lds()
         if boot is not None and not boot.fits(T, N, self.D, env.max_episode_steps):
             raise ValueError("rollout_linear: the bootstrap workspace was built for another rollout geometry")
+        # observation normaliser: the launch normalises the tile layer 0 reads; st.obs and the slots stay raw, and the
+        # critic launches below normalise their own input tiles (_fwd)
+        tables, nclip = self.obs_norm.kernel_args() if self.obs_norm is not None else (None, 0.0)
         _native.require().mlp_rollout(desc, self.rollout_lds_bytes(wlds), st.obs, st.actions, st.logp, st.entropy,
                                       st.rewards, st.dones, st.truncated, self.log_std, self.ac_scale, key_shift, seed,
                                       env.state, env.t, env.tg, env.ep_ret, env.ep_stats, env.env_ids, env.A, env.B,
                                       env.seed, env.max_episode_steps, env.frame_stack, wlds, stamps,
                                       None if boot is None else boot.final_obs,
-                                      None if boot is None else boot.final_step)
+                                      None if boot is None else boot.final_step, tables, nclip)
         self.value(st.obs.view((T + 1) * N, -1), st.values.view(-1))
         if boot is not None:
             from .returns import timeout_bootstrap_

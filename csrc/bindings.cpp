@@ -975,7 +975,7 @@ void mlp_fwd(Tensor desc, int64_t tw_base, int64_t ntw, int64_t mode, int64_t ld
              c10::optional<Tensor> v_old, c10::optional<Tensor> ent_coef, c10::optional<Tensor> kl_coef,
              double vf_coef, double ppo_clip, double v_clip, bool ppo, c10::optional<Tensor> g_log_std,
              c10::optional<Tensor> mstats, c10::optional<Tensor> mpart, c10::optional<Tensor> stamps,
-             c10::optional<Tensor> hdesc) {
+             c10::optional<Tensor> hdesc, c10::optional<Tensor> norm_tables, double norm_clip) {
   need(desc, at::kLong, "desc");
   TORCH_CHECK(desc.numel() * 8 >= (int64_t)(2 * sizeof(aca::MlpTower)), "mlp_fwd: desc too small");
   TORCH_CHECK(obs.is_cuda() && obs.scalar_type() == at::kFloat && obs.dim() == 2 && obs.stride(1) == 1,
@@ -1069,6 +1069,15 @@ void mlp_fwd(Tensor desc, int64_t tw_base, int64_t ntw, int64_t mode, int64_t ld
                                 (!gauss || a.g_log_std), "mlp_fwd: train needs actions, logp_old, adv (+ g_log_std)");
     if (ppo && v_clip > 0) TORCH_CHECK(a.v_old, "mlp_fwd: clipped value loss needs v_old");
   }
+  // running observation normalisation: tables [2, D] = mean32, istd32 (the launcher rejects them with mode 2)
+  if (has(norm_tables)) {
+    need(*norm_tables, at::kFloat, "norm_tables");
+    TORCH_CHECK(norm_tables->numel() == 2 * obs.size(1) && norm_clip > 0, "mlp_fwd: norm_tables must be [2, D] with a "
+                "positive clip");
+    a.norm_mean = ptr<float>(*norm_tables);
+    a.norm_istd = a.norm_mean + obs.size(1);
+    a.norm_clip = (float)norm_clip;
+  }
   check(aca_mlp_fwd(&a, (int)ntw, (size_t)lds, spec, cur_stream(obs)), "mlp_fwd");
 }
 
@@ -1157,7 +1166,8 @@ void mlp_rollout(Tensor desc, int64_t lds, Tensor obs, Tensor act, Tensor logp, 
                  Tensor done, Tensor trunc, Tensor log_std, Tensor ac_scale, int64_t key_shift, int64_t policy_seed,
                  Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, Tensor lin_A,
                  Tensor lin_B, int64_t env_seed, int64_t max_steps, int64_t k, bool wlds,
-                 c10::optional<Tensor> stamps, c10::optional<Tensor> final_obs, c10::optional<Tensor> final_step) {
+                 c10::optional<Tensor> stamps, c10::optional<Tensor> final_obs, c10::optional<Tensor> final_step,
+                 c10::optional<Tensor> norm_tables, double norm_clip) {
   need(desc, at::kLong, "desc");
   TORCH_CHECK(desc.numel() * 8 >= (int64_t)sizeof(aca::MlpTower), "mlp_rollout: desc too small");
   need(obs, at::kFloat, "obs");
@@ -1224,7 +1234,71 @@ void mlp_rollout(Tensor desc, int64_t lds, Tensor obs, Tensor act, Tensor logp, 
     a.final_step = ptr<int32_t>(*final_step);
     a.S = (int)S;
   }
+  // running observation normalisation: tables [2, D] = mean32, istd32 (storage and slots stay raw)
+  if (has(norm_tables)) {
+    need(*norm_tables, at::kFloat, "norm_tables");
+    TORCH_CHECK(norm_tables->numel() == 2 * D && norm_clip > 0, "mlp_rollout: norm_tables must be [2, D] with a "
+                "positive clip");
+    a.norm_mean = ptr<float>(*norm_tables);
+    a.norm_istd = a.norm_mean + D;
+    a.norm_clip = (float)norm_clip;
+  }
   check(aca_mlp_rollout(&a, (size_t)lds, cur_stream(obs)), "mlp_rollout");
+}
+
+// ---------------------------------------------------------------------------------------------- observation normaliser
+// state: fp64 [1 + 2 D] = count, mean, m2; tables: fp32 [2, D] = mean32, istd32; part: fp64 [obs_norm_parts(R), 2 D];
+// batch: fp64 [2 D + 1] = S1, S2, nb (obs_norm_args.h; oracle: ops/obs_norm.py)
+int64_t obs_norm_parts(int64_t R) { return aca_obs_norm_parts((int)R); }
+
+void obs_norm_prepare(Tensor obs, Tensor plane, Tensor tables, Tensor state, Tensor part, int64_t r_stat,
+                      double clip) {
+  TORCH_CHECK(obs.is_cuda() && obs.scalar_type() == at::kFloat && obs.dim() == 2 && obs.stride(1) == 1 &&
+                  obs.stride(0) >= obs.size(1), "obs_norm_prepare: obs must be fp32 [R, D] with unit column stride");
+  const int64_t R = obs.size(0), D = obs.size(1);
+  need(plane, at::kFloat, "plane");
+  need(tables, at::kFloat, "tables");
+  need(state, at::kDouble, "state");
+  need(part, at::kDouble, "part");
+  TORCH_CHECK(R < INT32_MAX && plane.numel() == R * D && tables.numel() == 2 * D && state.numel() == 1 + 2 * D &&
+                  part.numel() >= obs_norm_parts(R) * 2 * D && r_stat >= 0 && r_stat <= R && clip > 0,
+              "obs_norm_prepare: plane [R, D], tables [2, D], state [1 + 2 D], part [parts(R), 2 D], 0 <= r_stat <= R");
+  aca::ObsNormPrepArgs a{};
+  a.obs = ptr<float>(obs);
+  a.ld_obs = obs.stride(0);
+  a.plane = ptr<float>(plane);
+  a.tables = ptr<float>(tables);
+  a.state = ptr<double>(state);
+  a.part = ptr<double>(part);
+  a.R = (int)R;
+  a.D = (int)D;
+  a.R_stat = (int)r_stat;
+  a.clip = (float)clip;
+  check(aca_obs_norm_prepare(&a, cur_stream(obs)), "obs_norm_prepare");
+}
+
+// stage 0: part -> batch; 1: batch -> state, tables; 2: both in one launch
+void obs_norm_merge(c10::optional<Tensor> part, int64_t nparts, Tensor batch, double nb, Tensor state, Tensor tables,
+                    int64_t stage, double eps) {
+  need(batch, at::kDouble, "batch");
+  need(state, at::kDouble, "state");
+  need(tables, at::kFloat, "tables");
+  const int64_t D = tables.numel() / 2;
+  TORCH_CHECK(D >= 1 && tables.numel() == 2 * D && state.numel() == 1 + 2 * D && batch.numel() == 2 * D + 1,
+              "obs_norm_merge: tables [2, D], state [1 + 2 D], batch [2 D + 1]");
+  aca::ObsNormMergeArgs a{};
+  a.part = copt<double>(part, at::kDouble, "part");
+  a.nparts = (int)nparts;
+  if (stage != 1) TORCH_CHECK(nparts >= 0 && (nparts == 0 || (a.part && part->numel() >= nparts * 2 * D)),
+                              "obs_norm_merge: part must hold nparts rows of 2 D");
+  a.batch = ptr<double>(batch);
+  a.nb = nb;
+  a.state = ptr<double>(state);
+  a.tables = ptr<float>(tables);
+  a.D = (int)D;
+  a.stage = (int)stage;
+  a.eps = eps;
+  check(aca_obs_norm_merge(&a, cur_stream(batch)), "obs_norm_merge");
 }
 
 // words: CPU int64 [nseg, 13], fvals: CPU float [nseg, 4] (built once by ops/optim.py FusedGroupStep)
@@ -2054,7 +2128,8 @@ TORCH_LIBRARY(acamd, m) {
         "int A, Tensor? log_std, Tensor? ac_scale, Tensor? tg, Tensor? env_ids, int key_shift, int seed, "
         "Tensor? act_out, Tensor? logp_out, Tensor? ent_out, Tensor? v_out, Tensor? act_in, Tensor? logp_old, "
         "Tensor? adv, Tensor? ret, Tensor? v_old, Tensor? ent_coef, Tensor? kl_coef, float vf_coef, float ppo_clip, "
-        "float v_clip, bool ppo, Tensor? g_log_std, Tensor? mstats, Tensor? mpart=None, Tensor? stamps=None, Tensor? hdesc=None) -> ()");
+        "float v_clip, bool ppo, Tensor? g_log_std, Tensor? mstats, Tensor? mpart=None, Tensor? stamps=None, Tensor? hdesc=None, "
+        "Tensor? norm_tables=None, float norm_clip=0.0) -> ()");
   m.def("mlp_wgrad(Tensor items, int nrt, int nsplit, Tensor? g_log_std, int A, Tensor? ls_part, float ls_clip, "
         "Tensor? stats, Tensor ent_coef, Tensor kl_coef, Tensor mpart, int mpart_rows, Tensor? bump) -> ()");
   m.def("mlp_epoch_gather(Tensor obs, Tensor act, Tensor logp, Tensor adv, Tensor ret, Tensor? v, Tensor o_obs, "
@@ -2063,7 +2138,12 @@ TORCH_LIBRARY(acamd, m) {
         "Tensor done, Tensor truncated, Tensor log_std, Tensor ac_scale, int key_shift, int policy_seed, "
         "Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, Tensor lin_A, "
         "Tensor lin_B, int env_seed, int max_steps, int k, bool wlds, Tensor? stamps=None, Tensor? final_obs=None, "
-        "Tensor? final_step=None) -> ()");
+        "Tensor? final_step=None, Tensor? norm_tables=None, float norm_clip=0.0) -> ()");
+  m.def("obs_norm_parts(int R) -> int", &obs_norm_parts);
+  m.def("obs_norm_prepare(Tensor obs, Tensor plane, Tensor tables, Tensor state, Tensor part, int r_stat, "
+        "float clip) -> ()");
+  m.def("obs_norm_merge(Tensor? part, int nparts, Tensor batch, float nb, Tensor state, Tensor tables, int stage, "
+        "float eps) -> ()");
   m.def("timeout_bootstrap(Tensor rewards, Tensor final_step, Tensor v_final, float gamma) -> ()");
   m.def("gemm(Tensor A, int lda, bool a_k, Tensor B, int ldb, bool b_k, Tensor C, int ldc, int out_mode, int M, "
         "int N, int K, float alpha, Tensor? bias, bool relu, Tensor? mask, int ldm, Tensor? colsum, int colsum_mod, "
@@ -2151,6 +2231,8 @@ TORCH_LIBRARY_IMPL(acamd, CUDA, m) {
   m.impl("mlp_wgrad", &mlp_wgrad);
   m.impl("mlp_rollout", &mlp_rollout);
   m.impl("timeout_bootstrap", &timeout_bootstrap);
+  m.impl("obs_norm_prepare", &obs_norm_prepare);
+  m.impl("obs_norm_merge", &obs_norm_merge);
   m.impl("mlp_epoch_gather", &mlp_epoch_gather);
   m.impl("gemm", &gemm);
   m.impl("cnn_trunk_fwd", &cnn_trunk_fwd);

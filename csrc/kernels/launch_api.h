@@ -18,6 +18,7 @@
 #include "gemm_desc.h"
 #include "loss_args.h"
 #include "mlp_desc.h"
+#include "obs_norm_args.h"
 #include "optim_args.h"
 #include "ppo_head.h"
 #include "returns_args.h"
@@ -114,6 +115,11 @@ hipError_t aca_mlp_wgrad(const aca::WgradArgs* a, hipStream_t stream);
 hipError_t aca_mlp_epoch_gather(const aca::EpochGatherArgs* a, hipStream_t stream);
 hipError_t aca_mlp_tshadow(const aca::MlpTower* tw, int ntw, int total, hipStream_t stream);
 hipError_t aca_mlp_rollout(const aca::RolloutArgs* a, size_t lds, hipStream_t stream);
+
+// ---- running observation normalisation (obs_norm.hip)
+int aca_obs_norm_parts(int R);   // partial rows (= workgroups) of aca_obs_norm_prepare over R observation rows
+hipError_t aca_obs_norm_prepare(const aca::ObsNormPrepArgs* a, hipStream_t stream);
+hipError_t aca_obs_norm_merge(const aca::ObsNormMergeArgs* a, hipStream_t stream);
 
 // ---- GEMM and explicit conv plumbing (gemm*.hip, conv.hip)
 int aca_gemm_tile_dims(int tile, int* bm, int* bn);

@@ -732,11 +732,16 @@ __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* 
     __syncthreads();
     if (a.mode == 2) head_inputs();
     stamp(1);
-    // ---- input tile (gathered rows; padded rows / columns are zero)
+    // ---- input tile (gathered rows; padded rows / columns are zero). Rollout and evaluate launches normalise the raw
+    // observations as the tile is written (obs_norm_args.h; train launches read the pre-normalised plane)
+    const bool norm = a.norm_mean && a.mode != 2;
     for (int e = tid; e < MLP_BM * ld0; e += MLP_THREADS) {
       const int r = e / ld0, c = e - r * ld0;
       float v = 0.f;
-      if (r < rows && c < a.D) v = a.obs[S.grow[r] * a.ld_obs + c];
+      if (r < rows && c < a.D) {
+        v = a.obs[S.grow[r] * a.ld_obs + c];
+        if (norm) v = fminf(fmaxf((v - a.norm_mean[c]) * a.norm_istd[c], -a.norm_clip), a.norm_clip);
+      }
       X0[e] = v;
     }
   }
@@ -1521,7 +1526,12 @@ __device__ __forceinline__ void roll_layer_epilogue(const float* __restrict__ re
 // (ops/mlp.py supports_fused_rollout)
 // BOOT: the time-limit bootstrap's instantiation also keeps the terminal (pre-reset) observation stack of every
 // truncated step in a.final_obs / a.final_step; its extra stores exist in this instantiation only
-template <int KP0, bool BOOT>
+// NORM: running observation normalisation (obs_norm_args.h). The Xc / Xn tiles stay RAW -- the frame-stack shift, the
+// a.obs stores and the BOOT block read previous frames from them, and a shifted frame moves to a column with other
+// statistics -- and layer 0 reads one small normalised tile instead: filled from the step-0 tile at entry, refilled by
+// the thread that writes Xn, right after that write (the step's barriers already separate layer 0's reads from the
+// refill, so one buffer suffices). Tables and tile are static LDS of this instantiation only.
+template <int KP0, bool BOOT, bool NORM>
 __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // 16-byte base: the b128 LDS reads stay aligned
   __shared__ int64_t s_tg[ROLL_RB];
@@ -1537,6 +1547,9 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
   __shared__ int s_in[MLP_MAXL], s_out[MLP_MAXL], s_actc[MLP_MAXL];
   __shared__ int64_t s_wt[MLP_MAXL], s_b[MLP_MAXL];
   __shared__ float s_red[MLP_THREADS / 64 * 4 * 64];   // the layers' partial tiles (roll_layer_mfma)
+  // NORM: mean32 / istd32 of every column and layer 0's normalised input tile [ROLL_RB][ld0] (ld0 = KP0 + 4)
+  __shared__ float s_nm[NORM ? KP0 : 1], s_ni[NORM ? KP0 : 1];
+  __shared__ __attribute__((aligned(16))) float s_xq[NORM ? ROLL_RB * (KP0 + 4) : 4];
   const MlpTower& T = a.tw[0];
   const int nl = (int)T.nl;
   const int row0 = blockIdx.x * ROLL_RB;
@@ -1566,6 +1579,15 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
     s_er[tid] = live ? a.ep_ret[row0 + tid] : 0.f;
     if constexpr (BOOT) s_ne[tid] = 0;
   }
+  if constexpr (NORM) {
+    if (tid < KP0) {
+      s_nm[tid] = tid < D ? a.norm_mean[tid] : 0.f;
+      s_ni[tid] = tid < D ? a.norm_istd[tid] : 0.f;
+    }
+  }
+  [[maybe_unused]] auto normed = [&](float x, int c) {
+    return fminf(fmaxf((x - s_nm[c]) * s_ni[c], -a.norm_clip), a.norm_clip);
+  };
   __syncthreads();
   // diagnostics: 100 MHz stamps at phase boundaries (workgroup 0, wave 0 after the barrier), steps 0..15
   auto stamp = [&](int step, int slot) {
@@ -1615,6 +1637,8 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
     float v = 0.f;
     if (r < rows && c < D) v = a.obs[(size_t)(row0 + r) * D + c];
     sm[e] = v;
+    if constexpr (NORM)
+      if (e < ROLL_RB * ld0) s_xq[e] = (r < rows && c < D) ? normed(v, c) : 0.f;
   }
   for (int j = tid; j < LIN_OBS * LIN_OBS; j += MLP_THREADS) sA[j] = a.lin_A[j];
   for (int j = tid; j < LIN_OBS * LIN_ACT; j += MLP_THREADS) sB[j] = a.lin_B[j];
@@ -1666,7 +1690,7 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
     float* Y1 = sm + s_yo[1];
     float* Y2 = sm + s_yo[2];
     float* Y3 = sm + s_yo[3];
-    roll_layer_mfma<L0>(w0, Xc, ld0, s_red);
+    roll_layer_mfma<L0>(w0, NORM ? s_xq : Xc, ld0, s_red);
     __syncthreads();
     roll_layer_epilogue<L0>(s_red, bias_of(0, KP0 + 4), s_out[0], s_actc[0], Y0, 132);
     __syncthreads();
@@ -1787,9 +1811,11 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
             const float v = done ? y : pv[(f + 1) * LIN_OBS + r];
             xo[f * LIN_OBS + r] = v;
             go[f * LIN_OBS + r] = v;
+            if constexpr (NORM) s_xq[e * ld0 + f * LIN_OBS + r] = normed(v, f * LIN_OBS + r);
           }
           xo[(k - 1) * LIN_OBS + r] = y;
           go[(k - 1) * LIN_OBS + r] = y;
+          if constexpr (NORM) s_xq[e * ld0 + (k - 1) * LIN_OBS + r] = normed(y, (k - 1) * LIN_OBS + r);
         }
         if (owner) {
           const size_t o = (size_t)step * a.N + i;
@@ -1829,6 +1855,9 @@ extern "C" hipError_t aca_mlp_fwd(const MlpArgs* a, int ntw, size_t lds, int spe
   if (a->B <= 0) return hipSuccess;
   if (a->A > MLP_MAXA || a->D > MLP_MAXW || ntw < 1 || a->tw_base + ntw > 2 || !a->tw) return hipErrorInvalidValue;
   if (spec && (a->mode != 2 || a->tw_base != 0 || ntw != 2 || mlp_ngp2(a->D) != spec)) return hipErrorInvalidValue;
+  // observation tables: both or none, and never with a train launch (its rows are normalised already)
+  if ((a->norm_mean != nullptr) != (a->norm_istd != nullptr) || (a->norm_mean && a->mode == 2))
+    return hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
     const void* ks[4] = {reinterpret_cast<const void*>(&mlp_fwd_kernel<0>),
@@ -1875,6 +1904,8 @@ extern "C" hipError_t aca_mlp_tshadow(const MlpTower* tw, int ntw, int total, hi
 }
 
 constexpr size_t ROLLOUT_MAX_LDS = 150 * 1024;   // + ~9 KB static (s_red): within the 160 KB of a CU
+// the NORM instantiations hold their tables and normalised tile in static LDS too (1.6 KB at KP0 = 64)
+constexpr size_t ROLLOUT_NORM_LDS = 2 * 1024;
 
 extern "C" hipError_t aca_mlp_rollout(const RolloutArgs* a, size_t lds, hipStream_t stream) {
   if (a->N <= 0 || a->T <= 0) return hipSuccess;
@@ -1885,25 +1916,37 @@ extern "C" hipError_t aca_mlp_rollout(const RolloutArgs* a, size_t lds, hipStrea
   if (boot && (!a->final_step || a->max_steps < 1 ||
                (int64_t)a->S * a->max_steps < (int64_t)a->T))   // S < ceil(T / max_steps)
     return hipErrorInvalidValue;
+  // observation normalisation: both tables or none
+  const bool norm = a->norm_mean != nullptr;
+  if (norm != (a->norm_istd != nullptr)) return hipErrorInvalidValue;
   static bool attr = false;
   if (!attr) {
-    const void* ks[4] = {reinterpret_cast<const void*>(&mlp_rollout_kernel<32, false>),
-                         reinterpret_cast<const void*>(&mlp_rollout_kernel<64, false>),
-                         reinterpret_cast<const void*>(&mlp_rollout_kernel<32, true>),
-                         reinterpret_cast<const void*>(&mlp_rollout_kernel<64, true>)};
-    for (const void* k : ks)
-      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, ROLLOUT_MAX_LDS) != hipSuccess)
+    const void* ks[8] = {reinterpret_cast<const void*>(&mlp_rollout_kernel<32, false, false>),
+                         reinterpret_cast<const void*>(&mlp_rollout_kernel<64, false, false>),
+                         reinterpret_cast<const void*>(&mlp_rollout_kernel<32, true, false>),
+                         reinterpret_cast<const void*>(&mlp_rollout_kernel<64, true, false>),
+                         reinterpret_cast<const void*>(&mlp_rollout_kernel<32, false, true>),
+                         reinterpret_cast<const void*>(&mlp_rollout_kernel<64, false, true>),
+                         reinterpret_cast<const void*>(&mlp_rollout_kernel<32, true, true>),
+                         reinterpret_cast<const void*>(&mlp_rollout_kernel<64, true, true>)};
+    for (int i = 0; i < 8; ++i)
+      if (hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize,
+                              ROLLOUT_MAX_LDS - (i >= 4 ? ROLLOUT_NORM_LDS : 0)) != hipSuccess)
         return hipErrorInvalidValue;
     attr = true;
   }
-  if (lds > ROLLOUT_MAX_LDS) return hipErrorInvalidValue;
+  if (lds > ROLLOUT_MAX_LDS - (norm ? ROLLOUT_NORM_LDS : 0)) return hipErrorInvalidValue;
   const dim3 grid((a->N + ROLL_RB - 1) / ROLL_RB);
-  if (boot) {
-    if (a->k == 1) mlp_rollout_kernel<32, true><<<grid, MLP_THREADS, lds, stream>>>(*a);
-    else mlp_rollout_kernel<64, true><<<grid, MLP_THREADS, lds, stream>>>(*a);
-  } else {
-    if (a->k == 1) mlp_rollout_kernel<32, false><<<grid, MLP_THREADS, lds, stream>>>(*a);
-    else mlp_rollout_kernel<64, false><<<grid, MLP_THREADS, lds, stream>>>(*a);
+  const int which = (norm ? 4 : 0) | (boot ? 2 : 0) | (a->k == 1 ? 0 : 1);
+  switch (which) {
+    case 0: mlp_rollout_kernel<32, false, false><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    case 1: mlp_rollout_kernel<64, false, false><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    case 2: mlp_rollout_kernel<32, true, false><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    case 3: mlp_rollout_kernel<64, true, false><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    case 4: mlp_rollout_kernel<32, false, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    case 5: mlp_rollout_kernel<64, false, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    case 6: mlp_rollout_kernel<32, true, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    default: mlp_rollout_kernel<64, true, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
   }
   return hipGetLastError();
 }

@@ -54,6 +54,12 @@ struct MlpArgs {
   // train launches of the reference towers (mlp.hip SPEC path): a by-value copy of both tower descriptors, so the
   // weight-fragment pointers are kernel-argument (scalar) reads at entry, before any other memory round trip
   MlpTower htw[2];
+  // optional running observation normalisation (obs_norm_args.h), modes 0 and 1 of the generic path only: the input
+  // tile is written as clamp((x - norm_mean[c]) * norm_istd[c], +-norm_clip). Null = off. Train launches (mode 2) read
+  // the plane obs_norm_prepare wrote and never normalise (the launcher rejects tables with mode 2). Kept behind htw so
+  // that no existing field moves.
+  const float* norm_mean; const float* norm_istd;   // [D] each
+  float norm_clip;
 };
 
 struct WgradArgs {
@@ -96,6 +102,10 @@ struct RolloutArgs {
   float* final_obs;           // [N][S][D]; null: not kept
   int32_t* final_step;        // [N][S]: step of slot (i, s), -1 = unused (every slot is written by every launch)
   int S;
+  // optional (running observation normalisation, the NORM instantiations): layer 0 reads a normalised copy of the
+  // observation tile; a.obs, the frame-stack shift and final_obs stay raw. Null = off.
+  const float* norm_mean; const float* norm_istd;   // [D] each
+  float norm_clip;
 };
 
 }  // namespace aca
