@@ -5,9 +5,11 @@ The reference has no collective communication at all -- only the asynchronous pa
 mode: one process per GPU, each owning its own env bank (``env_offset = rank * N`` so every
 rank simulates different envs), identical parameters, and per update
 
-  * ONE all-reduce of the flat fp32 gradient slab (every parameter's gradient is a view into it, so there is no
-    bucketing bookkeeping: the whole model is one contiguous message -- 6.75 MB for the Atari CNN, one ring pass
-    over xGMI), averaged;
+  * the all-reduce of the flat fp32 (or bf16) gradient slab, averaged. Every parameter's gradient is a view into the
+    slab, so a message is a contiguous range of it with no per-parameter bookkeeping: the whole slab (6.75 MB for
+    the Atari CNN) per optimiser step, except strict A2C on the CNN engine, which sends two buckets -- the fc weight
+    (95 % of the bytes) while the conv backward runs, then the rest (``algos/trainer.py``, the comment above
+    ``_can_capture`` and ``_backward_allreduce_overlapped``);
   * ONE packed all-reduce of the scalar statistics that must be global (advantage sum / sum of squares / count
     for normalisation; the KL proxy for the adaptive lr), so every rank takes bit-identical optimiser steps.
 
