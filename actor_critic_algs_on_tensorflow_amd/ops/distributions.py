@@ -26,7 +26,15 @@ HALF_LOG_2PI = 0.5 * math.log(2 * math.pi)
 
 
 def _u_open(seed, keys, stream):
-    """Uniform in (0, 1): ((h >> 8) + 0.5) / 2^24, h = hash(seed, key_lo32, key_hi32, stream)."""
+    """Uniform in (0, 1]: ((h >> 8) + 0.5) / 2^24 in fp32, h = hash(seed, key_lo32, key_hi32, stream); negative keys
+    hash as their two's-complement words.
+
+    Never 0, but exactly 1.0 when ``h >> 8 == 0xFFFFFF`` (probability 2^-24): ``16777215 + 0.5`` rounds to 2^24 in
+    fp32, here and in ``uniform_open`` (csrc/kernels/common.h) alike. At ``u == 1`` the Gumbel noise ``-log(-log u)``
+    is +inf, so that action wins the argmax (log-prob and entropy stay finite); as ``u1`` of a Box-Muller pair it
+    makes the radius 0, so ``eps == 0`` and the action is the mean. The smallest value, ``0.5 * 2^-24``, bounds the
+    Gumbel noise below by -2.86 and the Box-Muller radius above by 5.89. The bits are part of the recorded streams
+    (parity fixtures, checkpoints) and must not change."""
     keys = torch.as_tensor(keys, dtype=torch.int64)
     h = rng.hash_u32(seed, keys & rng.M32, (keys >> 32) & rng.M32, stream)
     return ((h >> 8).to(torch.float32) + 0.5) * (1.0 / 16777216.0)
@@ -51,9 +59,18 @@ def categorical_sample_ref(logits, keys, seed):
     return act, logp, ent
 
 
+MAX_NATIVE_ACTIONS = 64   # one 64-lane wave per row (csrc/kernels/heads.hip); the binding refuses more
+
+
+def _categorical_native(logits):
+    """The HIP kernel serves GPU logits of at most 64 actions; wider discrete spaces sample through the PyTorch oracle
+    on the tensor's own device (same keys, same stream, one lane per action)."""
+    return _native.use_native(logits) and logits.shape[-1] <= MAX_NATIVE_ACTIONS
+
+
 def categorical_sample(logits, keys, seed=0):
     """-> (actions int32 [B], logp fp32 [B], entropy fp32 [B])."""
-    if _native.use_native(logits):
+    if _categorical_native(logits):
         B = logits.shape[0]
         act = torch.empty(B, dtype=torch.int32, device=logits.device)
         logp = torch.empty(B, dtype=torch.float32, device=logits.device)

@@ -44,7 +44,12 @@ __device__ __forceinline__ float uniform01(uint32_t seed, uint32_t env, uint32_t
   return (float)(hash_u32(seed, env, step, stream) >> 8) * (1.0f / 16777216.0f);
 }
 
-// (0, 1) open interval (policy sampling); key = 64-bit per-row key split into (lo, hi) words
+// (0, 1] (policy sampling); key = 64-bit per-row key split into (lo, hi) words, negative keys as their two's-complement
+// words. Never 0; exactly 1.0 when h >> 8 == 0xFFFFFF (probability 2^-24), because 16777215 + 0.5 rounds to 2^24 in
+// fp32 (ops/distributions.py _u_open rounds the same way). At u == 1 the Gumbel noise -log(-log u) is +inf -- that lane
+// wins the argmax, log-prob and entropy stay finite -- and the Box-Muller radius sqrt(-2 log u1) is 0 (eps == 0, the
+// action is the mean); u2 == 1 gives cos(2 pi) like u2 -> 0. The smallest value is 0.5 * 2^-24: Gumbel noise >= -2.86,
+// Box-Muller radius <= 5.89. The bits are part of the recorded streams (parity fixtures, checkpoints): do not change.
 __device__ __forceinline__ float uniform_open(uint32_t seed, int64_t key, uint32_t stream) {
   uint32_t lo = (uint32_t)((uint64_t)key & 0xFFFFFFFFull);
   uint32_t hi = (uint32_t)(((uint64_t)key >> 32) & 0xFFFFFFFFull);
@@ -245,8 +250,9 @@ __device__ __forceinline__ CatSample cat_sample(float zin, int A, int lane, uint
   const float z = on ? zin : -INFINITY;
   const float m = red_max<W>(z);
   const float ex = on ? expf(z - m) : 0.f;
-  const float lse = m + logf(red_sum<W>(ex));
-  const float lp = z - lse;
+  // (z - m) - log(sum), not z - (m + log(sum)): m + log(sum) rounds to the ulp of m, which absorbs log(sum) entirely
+  // once |m| >= 2^24 (logits 2^30 in k tied lanes gave log-prob 0 and entropy 0 instead of -log k and log k)
+  const float lp = (z - m) - logf(red_sum<W>(ex));
   const float H = red_sum<W>(on ? -expf(lp) * lp : 0.f);
   float best = -INFINITY;
   if (on) best = z + (-logf(-logf(uniform_open(seed, key, (uint32_t)lane))));

@@ -73,6 +73,20 @@ def test_mlp_policy_step_and_evaluate(cuda, case):
     out = torch.empty(N, device=cuda)
     eng.value(obs, out)
     torch.testing.assert_close(out, v_e, rtol=1e-4, atol=1e-5)
+    if disc:
+        # decisive-row rule (tests/oracles/sampling_oracle.py) on top of the agreement share above: wherever the fp64
+        # gap of the reference model's perturbed logits exceeds the margin (widened by 4 x the engine's measured
+        # difference from that model on these rows), the engine's action is the oracle's
+        import os
+        import sys
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "oracles"))
+        import sampling_oracle as O
+        o = O.categorical(pi, keys, 1234)
+        diff = max(float((v - v_ref).abs().max()), float((lp2 - lp_e).abs().max()), float((ent2 - ent_e).abs().max()))
+        dec = O.decisive(o["gap"], O.MARGIN + 4 * diff)
+        assert float(dec.double().mean()) >= 0.95
+        assert torch.equal(act.cpu().long()[dec], o["act"][dec])
+        torch.testing.assert_close(logp.cpu()[dec], o["logp"].float()[dec], rtol=1e-4, atol=1e-4)
 
 
 def _ref_grads(ref, obs, act, lo, adv, ret, v_old, ppo, beta, ce, clip, vclip):
