@@ -138,6 +138,8 @@ class ActorCriticTrainer:
         self.flat = FlatParams(self.model.param_groups(), self.device)
         if cfg.norm_obs:
             self._check_norm_obs()
+        if cfg.norm_reward:
+            self._check_norm_reward()
         if dp is not None:
             dp.broadcast_params(self.flat)
             if cfg.grad_bucket_dtype == "bf16" and dp.compress is None:
@@ -210,6 +212,12 @@ class ActorCriticTrainer:
             self.obs_norm.reserve(T * N)
             if self.mlp is not None:
                 self.mlp.obs_norm = self.obs_norm
+        # running reward scaling (ops/reward_norm.py): every collect variant scales st.rewards in place right after the
+        # rollout wrote them raw and before any bootstrap term is added; episode-return logging (env.ep_ret) stays raw
+        self.reward_norm = None
+        if cfg.norm_reward:
+            from ..ops.reward_norm import RewardNormalizer
+            self.reward_norm = RewardNormalizer(N, cfg.gamma, cfg.reward_clip, 1e-8, self.device)
         dev = self.device
         self.ent_coef = torch.tensor(cfg.ent_coef, device=dev)
         self.kl_coef = torch.tensor(cfg.kl_coef, device=dev)
@@ -258,6 +266,24 @@ class ActorCriticTrainer:
                              "basic_ac) keep the reference's raw observations; use a2c or ppo")
         if len(self.env.obs_shape) != 1 or self.env.obs_dtype != torch.float32:
             raise ValueError("norm_obs=True needs fp32 vector observations")
+
+    def _check_norm_reward(self):
+        """``norm_reward`` covers the MLP models under a2c / ppo, whose returns are computed from ``storage.rewards``
+        after the rollout."""
+        from ..models.policy import CNNActorCritic
+        if isinstance(self.model, CNNActorCritic):
+            raise ValueError("norm_reward=True with a CNN model: the native A2C head computes returns in-kernel from "
+                             "the stored rewards and Atari rewards are unit-scale; reward scaling is for the MLP "
+                             "models")
+        if self.cfg.algo not in ("a2c", "ppo"):
+            raise ValueError(f"norm_reward=True with algo={self.cfg.algo!r}: the reference-parity trainers (a3c, "
+                             "basic_ac) keep the reference's raw rewards; use a2c or ppo")
+
+    def _scale_rewards(self):
+        """After the rollout wrote the raw rewards, before any bootstrap term: scan, merge (under DP one small
+        collective, between rollout and returns) and scale in place."""
+        st = self.storage
+        self.reward_norm.update_(st.rewards, st.dones, self.dp, self._comm)
 
     def _nobs(self, obs):
         """Torch engine: what a tower reads for the raw observations ``obs``."""
@@ -317,6 +343,13 @@ class ActorCriticTrainer:
         if self.engine is not None:
             return self._collect_native()
         st, env, model = self.storage, self.env, self.model
+        # reward scaling: the scan sees raw env rewards only, so the per-step bootstrap terms (critic units: already
+        # scaled) wait in a side buffer and are added after the scaling
+        side = None
+        if self.reward_norm is not None and self.cfg.bootstrap_on_timeout:
+            side = getattr(self, "_boot_side", None)
+            if side is None:
+                side = self._boot_side = torch.zeros_like(st.rewards)
         for t in range(st.T):
             obs_t = st.obs[t]
             pi, v = model(self._nobs(obs_t))
@@ -332,7 +365,14 @@ class ActorCriticTrainer:
                 # reset observation already sits in obs[t+1]); the truncated step's reward gets gamma * V(terminal
                 # observation) -- the observation the auto-reset overwrote, kept by the bank in final_obs
                 vf = model.value(self._nobs(env.final_obs))
-                st.rewards[t].add_(self.cfg.gamma * vf * st.truncated[t].to(vf.dtype))
+                if side is None:
+                    st.rewards[t].add_(self.cfg.gamma * vf * st.truncated[t].to(vf.dtype))
+                else:
+                    side[t].copy_(self.cfg.gamma * vf * st.truncated[t].to(vf.dtype))
+        if self.reward_norm is not None:
+            self._scale_rewards()
+            if side is not None:
+                st.rewards.add_(side)
         st.values[st.T].copy_(model.value(self._nobs(st.obs[st.T])))
 
     @torch.no_grad()
@@ -347,7 +387,8 @@ class ActorCriticTrainer:
             # time-limit bootstrap: the launch keeps the truncated steps' terminal observations in compact slots; one
             # critic launch over the slots and one fix-up launch put gamma * V(terminal observation) into the rewards
             eng.rollout_linear(env, st, KEY_ENV_BITS, self.policy_seed,
-                               boot=self._timeout_boot_ws() if boot else None)
+                               boot=self._timeout_boot_ws() if boot else None,
+                               after_rollout=self._scale_rewards if self.reward_norm is not None else None)
             return
         if boot and getattr(self, "_final_obs", None) is None:
             self._final_obs = torch.zeros((st.T,) + tuple(st.obs.shape[1:]), dtype=st.obs.dtype, device=self.device)
@@ -359,6 +400,8 @@ class ActorCriticTrainer:
                      done_out=st.dones[t], trunc_out=st.truncated[t],
                      final_out=self._final_obs[t] if boot else None)
         eng.value(st.obs[st.T], st.values[st.T])
+        if self.reward_norm is not None:
+            self._scale_rewards()   # raw env rewards; the bootstrap term below is added unscaled
         if boot:
             # a time-limit cut stays an episode boundary (done = 1); the truncated step's reward gets
             # gamma * V(terminal observation): ONE critic launch over the T x N terminal stacks the env kernel wrote

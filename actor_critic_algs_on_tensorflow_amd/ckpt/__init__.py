@@ -17,7 +17,9 @@ This module writes and reads the same files through the C++ codec (:mod:`.codec`
 * any other model (the Atari CNN): ``acamd/<module path>`` names.
 * native resume state (not in the reference, which cannot resume -- SURVEY §5.4) goes under ``_acamd/...`` keys:
   optimiser moments/step/lr per group, iteration and env-step counters, env-bank state, and -- for a ``norm_obs``
-  trainer -- the observation normaliser as fp64 tensors ``_acamd/obs_norm/{count,mean,m2,clip}``. TF ignores unknown
+  trainer -- the observation normaliser as fp64 tensors ``_acamd/obs_norm/{count,mean,m2,clip}``; for a ``norm_reward``
+  trainer the reward scaler's statistics as fp64 ``_acamd/reward_norm/{count,mean,m2,clip,gamma}`` and its per-env
+  running return as fp64 ``reward_ret`` beside the env-bank tensors (per rank). TF ignores unknown
   keys only if they are not requested, so reference tooling can still restore the model variables.
 
 A ``checkpoint`` state file (``model_checkpoint_path: "..."``) is written next to the bundles and the newest
@@ -142,10 +144,24 @@ def env_prefix(env_id):
     return env_id.split("-")[0]
 
 
+REWARD_RET = "reward_ret"
+REWARD_NORM_PREFIX = "_acamd/reward_norm/"
+_REWARD_NORM_KEYS = ("count", "mean", "m2", "clip", "gamma")
+
+
+def _env_tensor(k, v):
+    """A gathered env-bank tensor as it is stored: the reward scaler's returns as numpy float64 (``_to_np`` would
+    store a floating tensor as fp32 and break bit-exact resume)."""
+    return v.detach().cpu().numpy().astype(np.float64) if k == REWARD_RET else v
+
+
 def _env_state(trainer):
     env = trainer.env
     st = {k: getattr(env, k) for k in ("state", "t", "tg", "ep_ret")}
     st["obs"] = trainer.storage.obs[0]
+    rn = getattr(trainer, "reward_norm", None)
+    if rn is not None:   # the per-env running discounted return: local to the rank, like the bank
+        st[REWARD_RET] = rn.ret
     return st
 
 
@@ -235,11 +251,11 @@ def save_trainer(trainer, path=None):
     tensors["_acamd/iteration"] = np.asarray(trainer.iteration, dtype=np.int64)
     tensors["_acamd/env_steps"] = np.asarray(trainer.env_steps, dtype=np.int64)
     for k, v in envs[0].items():
-        tensors[f"_acamd/env/{k}"] = v
+        tensors[f"_acamd/env/{k}"] = _env_tensor(k, v)
     if len(envs) > 1:
         for r, st in envs.items():
             for k, v in st.items():
-                tensors[f"_acamd/env/rank{r}/{k}"] = v
+                tensors[f"_acamd/env/rank{r}/{k}"] = _env_tensor(k, v)
     tensors["_acamd/world_size"] = np.asarray(len(envs), dtype=np.int64)
     tensors["_acamd/update_counter"] = trainer.update_counter
     tensors["_acamd/ent_coef"] = trainer.ent_coef
@@ -248,6 +264,10 @@ def save_trainer(trainer, path=None):
     if norm is not None:   # numpy float64: tensors would be stored as fp32 (_to_np)
         for k, v in norm.state_dict().items():
             tensors[OBS_NORM_PREFIX + k] = v.numpy().astype(np.float64)
+    rn = getattr(trainer, "reward_norm", None)
+    if rn is not None:
+        for k, v in rn.state_dict().items():
+            tensors[REWARD_NORM_PREFIX + k] = v.numpy().astype(np.float64)
     save_tensors(path, tensors)
     directory = os.path.dirname(path) or "."
     kept = _prune(directory, os.path.basename(path).rsplit("-", 1)[0], cfg.keep_checkpoints)
@@ -268,6 +288,18 @@ def obs_norm_state(tensors):
     if len(have) != len(keys):
         raise KeyError(f"checkpoint lacks {sorted(set(keys) - set(have))}")
     return {k[len(OBS_NORM_PREFIX):]: torch.as_tensor(np.array(tensors[k], dtype=np.float64)) for k in keys}
+
+
+def reward_norm_state(tensors):
+    """The reward scaler's statistics in a bundle (``{count, mean, m2, clip, gamma}`` as fp64 tensors), or None when
+    the bundle was written without ``norm_reward``."""
+    keys = [REWARD_NORM_PREFIX + k for k in _REWARD_NORM_KEYS]
+    have = [k for k in keys if k in tensors]
+    if not have:
+        return None
+    if len(have) != len(keys):
+        raise KeyError(f"checkpoint lacks {sorted(set(keys) - set(have))}")
+    return {k[len(REWARD_NORM_PREFIX):]: torch.as_tensor(np.array(tensors[k], dtype=np.float64)) for k in keys}
 
 
 def _assign(dst, arr):
@@ -311,14 +343,24 @@ def load_trainer(trainer, path):
                            f"{[OBS_NORM_PREFIX + k for k in ('count', 'mean', 'm2', 'clip')]} that a norm_obs=True "
                            "trainer restores (it was written with norm_obs=False)")
         norm.load_state_dict(sd)
+    # the per-rank tensors (env banks, the reward scaler's returns) of this rank
+    world, rank = getattr(trainer, "world", 1), getattr(trainer, "rank", 0)
+    saved = int(t["_acamd/world_size"]) if "_acamd/world_size" in t else 1
+    if "_acamd/iteration" in t and saved != world:
+        raise ValueError(f"checkpoint {path} holds the env banks of {saved} rank(s); this job has {world}")
+    pre = f"_acamd/env/rank{rank}/" if saved > 1 else "_acamd/env/"
+    rn = getattr(trainer, "reward_norm", None)
+    if rn is not None:   # (a norm_reward=False trainer ignores the tensors)
+        sd = reward_norm_state(t)
+        if sd is None or pre + REWARD_RET not in t:
+            raise KeyError(f"checkpoint {path} lacks the reward scaler tensors "
+                           f"{[REWARD_NORM_PREFIX + k for k in _REWARD_NORM_KEYS] + [pre + REWARD_RET]} that a "
+                           "norm_reward=True trainer restores (it was written with norm_reward=False)")
+        sd["ret"] = torch.as_tensor(np.array(t[pre + REWARD_RET], dtype=np.float64))
+        rn.load_state_dict(sd)
     if "_acamd/iteration" in t:
         trainer.iteration = int(t["_acamd/iteration"])
         trainer.env_steps = int(t["_acamd/env_steps"])
-        world, rank = getattr(trainer, "world", 1), getattr(trainer, "rank", 0)
-        saved = int(t["_acamd/world_size"]) if "_acamd/world_size" in t else 1
-        if saved != world:
-            raise ValueError(f"checkpoint {path} holds the env banks of {saved} rank(s); this job has {world}")
-        pre = f"_acamd/env/rank{rank}/" if saved > 1 else "_acamd/env/"
         for k in ("state", "t", "tg", "ep_ret"):
             _assign(getattr(trainer.env, k), t[pre + k])
         _assign(trainer.storage.obs[0], t[pre + "obs"])
@@ -339,4 +381,5 @@ def detect_variant(names):
 
 
 __all__ = ["codec", "save_trainer", "load_trainer", "save_tensors", "load_tensors", "load_model",
-           "reference_tensors", "model_tensors", "latest_checkpoint", "detect_variant", "obs_norm_state"]
+           "reference_tensors", "model_tensors", "latest_checkpoint", "detect_variant", "obs_norm_state",
+           "reward_norm_state"]

@@ -34,6 +34,8 @@ def build_parser():
     p.add_argument("--quiet", action="store_true")
     p.add_argument("--norm-obs", action="store_true",
                    help="running observation normalisation (TrainConfig.norm_obs; --algo a2c|ppo, MLP models)")
+    p.add_argument("--norm-reward", action="store_true",
+                   help="running return-based reward scaling (TrainConfig.norm_reward; --algo a2c|ppo, MLP models)")
     return p
 
 
@@ -53,6 +55,8 @@ def main(argv=None):
         kw["num_envs"] = a.num_envs
     if a.norm_obs:
         kw["norm_obs"] = True
+    if a.norm_reward:
+        kw["norm_reward"] = True
     cfg = preset(name, **kw)
     res = train(cfg)
     print("done: %d iterations, %d env steps, %.1f env-steps/s" % (res.iterations, res.env_steps,

@@ -95,6 +95,12 @@ class TrainConfig:
     # update; its rollout's observations are merged after its learner. MLP models under a2c / ppo only
     norm_obs: bool = False
     obs_clip: float = 10.0
+    # running return-based reward scaling (ops/reward_norm.py): after each rollout the raw rewards are divided by the
+    # running standard deviation of the per-env discounted return and clipped to +-reward_clip; no mean is subtracted.
+    # The statistics include the rollout they scale (rewards never feed the policy, so nothing has to stay frozen as
+    # with norm_obs); a time-limit bootstrap term is added after the scaling. MLP models under a2c / ppo only
+    norm_reward: bool = False
+    reward_clip: float = 10.0
     # -- losses ------------------------------------------------------------------------------------------------
     ent_coef: float = 0.01            # reference "gamma" (Basic_AC/policies.py:38)
     kl_coef: float = 0.0              # reference "beta" (squared log-prob drift proxy)
@@ -177,6 +183,16 @@ class TrainConfig:
                                  "in-kernel; observation normalisation is for the MLP models")
             if not self.obs_clip > 0:
                 raise ValueError(f"TrainConfig.obs_clip={self.obs_clip}: must be > 0")
+        if self.norm_reward:
+            if self.algo in ("a3c", "basic_ac"):
+                raise ValueError(f"TrainConfig.norm_reward=True with algo={self.algo!r}: the reference-parity trainers "
+                                 "keep the reference's raw rewards; use a2c or ppo")
+            if self.model == "cnn":
+                raise ValueError("TrainConfig.norm_reward=True with model='cnn': the native A2C head computes returns "
+                                 "in-kernel from the stored rewards and Atari rewards are unit-scale; reward scaling "
+                                 "is for the MLP models")
+            if not self.reward_clip > 0:
+                raise ValueError(f"TrainConfig.reward_clip={self.reward_clip}: must be > 0")
         if self.look_ahead is not None and int(self.look_ahead) < 1:
             raise ValueError(f"TrainConfig.look_ahead={self.look_ahead}: must be >= 1 (None = the whole rollout)")
 

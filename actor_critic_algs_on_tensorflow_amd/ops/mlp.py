@@ -348,7 +348,7 @@ class MLPEngine:
         cap = self.ROLLOUT_MAX_LDS - (self.ROLLOUT_NORM_LDS if self.obs_norm is not None else 0)
         return self.rollout_lds_bytes(True) <= cap
 
-    def rollout_linear(self, env, st, key_shift, seed, stamps=None, boot=None):
+    def rollout_linear(self, env, st, key_shift, seed, stamps=None, boot=None, after_rollout=None):
         """T steps of policy + env for the whole bank in one launch, then V(s) of all (T+1) N observations in one
         critic launch. Equal to T x (:meth:`policy_step` + ``env.step``) + :meth:`value` up to the actor's fp32
         summation order (4x4x1 tiles with the K range split over waves vs 16x16x4 tiles): same RNG keys and resets.
@@ -357,7 +357,10 @@ class MLPEngine:
         time-limit bootstrap (with an observation normaliser attached the slots hold raw stacks, normalised by the
         critic launch that values them). The rollout launch keeps the terminal observation of every truncated step in the
         workspace's slots, one more critic launch values the ``N S`` slots and one fix-up launch adds
-        ``gamma V(terminal observation)`` to those steps' rewards (unused slots are valued but never read)."""
+        ``gamma V(terminal observation)`` to those steps' rewards (unused slots are valued but never read).
+
+        ``after_rollout`` (a callable, optional) runs right after the rollout launch, when ``st.rewards`` holds the raw
+        env rewards and before the fix-up launch adds any bootstrap term: the trainer's reward scaling."""
         T, N = st.T, env.num_envs
         desc, _ = self.desc(None)
         wlds = self.rollout_weights_in_lds()
@@ -372,6 +375,8 @@ class MLPEngine:
                                       env.seed, env.max_episode_steps, env.frame_stack, wlds, stamps,
                                       None if boot is None else boot.final_obs,
                                       None if boot is None else boot.final_step, tables, nclip)
+        if after_rollout is not None:
+            after_rollout()
         self.value(st.obs.view((T + 1) * N, -1), st.values.view(-1))
         if boot is not None:
             from .returns import timeout_bootstrap_

@@ -1301,6 +1301,55 @@ void obs_norm_merge(c10::optional<Tensor> part, int64_t nparts, Tensor batch, do
   check(aca_obs_norm_merge(&a, cur_stream(batch)), "obs_norm_merge");
 }
 
+// ---------------------------------------------------------------------------------------------- reward scaler
+// rewards: fp32 [T, N] raw; dones: uint8 [T, N]; ret: fp64 [N]; state: fp64 [3] = count, mean, m2; part: fp64 [N, 2];
+// tables: fp32 [2] = mean32, istd32 (reward_norm_args.h; oracle: ops/reward_norm.py). The merge is obs_norm_merge, D = 1.
+int64_t reward_norm_unroll() { return aca_reward_norm_unroll(); }
+
+void reward_norm_scan(Tensor rewards, Tensor dones, Tensor ret, Tensor state, Tensor part, double gamma) {
+  for (const Tensor* t : {&rewards, &dones, &ret, &state, &part})
+    TORCH_CHECK(t->is_cuda() && t->device() == rewards.device(), "reward_norm_scan: every operand on one GPU");
+  TORCH_CHECK(rewards.scalar_type() == at::kFloat && rewards.dim() == 2, "reward_norm_scan: rewards must be fp32 [T, N], "
+              "got ", rewards.scalar_type(), " with ", rewards.dim(), " dims");
+  TORCH_CHECK(dones.scalar_type() == at::kByte && dones.dim() == 2 && dones.sizes() == rewards.sizes(),
+              "reward_norm_scan: dones must be uint8 [T, N] like rewards, got ", dones.scalar_type());
+  const int64_t T = rewards.size(0), N = rewards.size(1);
+  TORCH_CHECK(T >= 1 && N >= 1 && T < INT32_MAX && N < INT32_MAX, "reward_norm_scan: T >= 1, N >= 1");
+  need(ret, at::kDouble, "ret");
+  need(state, at::kDouble, "state");
+  need(part, at::kDouble, "part");
+  TORCH_CHECK(ret.numel() == N && state.numel() == 3 && part.numel() >= 2 * N,
+              "reward_norm_scan: ret [N], state [3], part [N, 2] for rewards [T, N]");
+  aca::RewardNormScanArgs a{};
+  a.rewards = ptr<float>(rewards);
+  a.r_stride_t = rewards.stride(0);
+  a.r_stride_n = rewards.stride(1);
+  a.dones = ptr<uint8_t>(dones);
+  a.d_stride_t = dones.stride(0);
+  a.d_stride_n = dones.stride(1);
+  a.ret = ptr<double>(ret);
+  a.ret_len = ret.numel();
+  a.state = ptr<double>(state);
+  a.part = ptr<double>(part);
+  a.T = (int)T;
+  a.N = (int)N;
+  a.gamma = gamma;
+  check(aca_reward_norm_scan(&a, cur_stream(rewards)), "reward_norm_scan");   // (rejects strides other than (N, 1))
+}
+
+void reward_norm_apply(Tensor rewards, Tensor tables, double clip) {
+  need(rewards, at::kFloat, "rewards");
+  need(tables, at::kFloat, "tables");
+  TORCH_CHECK(tables.device() == rewards.device() && tables.numel() == 2 && rewards.numel() >= 1 && clip > 0,
+              "reward_norm_apply: tables [2] on the rewards' GPU, a positive clip");
+  aca::RewardNormApplyArgs a{};
+  a.rewards = ptr<float>(rewards);
+  a.n = rewards.numel();
+  a.tables = ptr<float>(tables);
+  a.clip = (float)clip;
+  check(aca_reward_norm_apply(&a, cur_stream(rewards)), "reward_norm_apply");
+}
+
 // words: CPU int64 [nseg, 13], fvals: CPU float [nseg, 4] (built once by ops/optim.py FusedGroupStep)
 void opt_multi(Tensor words, Tensor fvals, c10::optional<Tensor> trans, bool adam, double b1, double b2, double eps,
                bool zero_grad, Tensor stream_ref, int64_t t_off) {
@@ -2144,6 +2193,9 @@ TORCH_LIBRARY(acamd, m) {
         "float clip) -> ()");
   m.def("obs_norm_merge(Tensor? part, int nparts, Tensor batch, float nb, Tensor state, Tensor tables, int stage, "
         "float eps) -> ()");
+  m.def("reward_norm_unroll() -> int", &reward_norm_unroll);
+  m.def("reward_norm_scan(Tensor rewards, Tensor dones, Tensor ret, Tensor state, Tensor part, float gamma) -> ()");
+  m.def("reward_norm_apply(Tensor rewards, Tensor tables, float clip) -> ()");
   m.def("timeout_bootstrap(Tensor rewards, Tensor final_step, Tensor v_final, float gamma) -> ()");
   m.def("gemm(Tensor A, int lda, bool a_k, Tensor B, int ldb, bool b_k, Tensor C, int ldc, int out_mode, int M, "
         "int N, int K, float alpha, Tensor? bias, bool relu, Tensor? mask, int ldm, Tensor? colsum, int colsum_mod, "
@@ -2233,6 +2285,8 @@ TORCH_LIBRARY_IMPL(acamd, CUDA, m) {
   m.impl("timeout_bootstrap", &timeout_bootstrap);
   m.impl("obs_norm_prepare", &obs_norm_prepare);
   m.impl("obs_norm_merge", &obs_norm_merge);
+  m.impl("reward_norm_scan", &reward_norm_scan);
+  m.impl("reward_norm_apply", &reward_norm_apply);
   m.impl("mlp_epoch_gather", &mlp_epoch_gather);
   m.impl("gemm", &gemm);
   m.impl("cnn_trunk_fwd", &cnn_trunk_fwd);

@@ -22,6 +22,7 @@
 #include "optim_args.h"
 #include "ppo_head.h"
 #include "returns_args.h"
+#include "reward_norm_args.h"
 
 extern "C" {
 
@@ -120,6 +121,11 @@ hipError_t aca_mlp_rollout(const aca::RolloutArgs* a, size_t lds, hipStream_t st
 int aca_obs_norm_parts(int R);   // partial rows (= workgroups) of aca_obs_norm_prepare over R observation rows
 hipError_t aca_obs_norm_prepare(const aca::ObsNormPrepArgs* a, hipStream_t stream);
 hipError_t aca_obs_norm_merge(const aca::ObsNormMergeArgs* a, hipStream_t stream);
+
+// ---- running reward scaling (reward_norm.hip; its merge is aca_obs_norm_merge with D = 1)
+int aca_reward_norm_unroll(void);   // RWN_UNROLL: time steps per load round of the scan
+hipError_t aca_reward_norm_scan(const aca::RewardNormScanArgs* a, hipStream_t stream);
+hipError_t aca_reward_norm_apply(const aca::RewardNormApplyArgs* a, hipStream_t stream);
 
 // ---- GEMM and explicit conv plumbing (gemm*.hip, conv.hip)
 int aca_gemm_tile_dims(int tile, int* bm, int* bn);

@@ -3,7 +3,7 @@
 
     python scripts/bench_configs.py [--configs pong_a2c,breakout_ppo,mujoco_ppo_dp8,cartpole_cpu] [--updates K]
                                     [--warmup W] [--engine auto|torch] [--device cuda:0] [--engine-opts JSON]
-                                    [--bootstrap-on-timeout] [--norm-obs]
+                                    [--bootstrap-on-timeout] [--norm-obs] [--norm-reward]
 
 Each config runs with its preset (config.py PRESETS): same model, env bank, rollout length, optimiser and PPO
 epochs/minibatches as BASELINE.json names; synthetic envs and random-init weights. The update is captured as a
@@ -25,7 +25,7 @@ import torch  # noqa: E402
 
 
 def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None, bootstrap_on_timeout=False,
-        norm_obs=False):
+        norm_obs=False, norm_reward=False):
     from actor_critic_algs_on_tensorflow_amd import preset
     from actor_critic_algs_on_tensorflow_amd.algos.trainer import ActorCriticTrainer
     dev = device if name != "cartpole_cpu" or device == "cpu" else device
@@ -35,6 +35,8 @@ def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None
         cfg.bootstrap_on_timeout = True
     if norm_obs:
         cfg = cfg.replace(norm_obs=True)   # (validated: MLP configs only)
+    if norm_reward:
+        cfg = cfg.replace(norm_reward=True)   # (validated: MLP configs only)
     if engine_opts:
         import dataclasses
         cfg.engine_opts = dataclasses.replace(cfg.engine_opts, **engine_opts)
@@ -70,7 +72,7 @@ def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None
             "engine": "native-cnn" if tr.engine is not None else ("native-mlp" if tr.mlp is not None else "torch"),
             "hipgraph": bool(tr.graph), "device": dev, "dp_world1": bool(dp_world1),
             "engine_opts": engine_opts or {}, "bootstrap_on_timeout": bool(cfg.bootstrap_on_timeout),
-            "norm_obs": bool(cfg.norm_obs),
+            "norm_obs": bool(cfg.norm_obs), "norm_reward": bool(cfg.norm_reward),
             "ppo": {"epochs": cfg.ppo_epochs, "minibatches": cfg.ppo_minibatches} if cfg.algo == "ppo" else None}
 
 
@@ -91,11 +93,13 @@ def main():
                     help="set TrainConfig.bootstrap_on_timeout on the chosen configs")
     ap.add_argument("--norm-obs", action="store_true",
                     help="set TrainConfig.norm_obs on the chosen configs (MLP models)")
+    ap.add_argument("--norm-reward", action="store_true",
+                    help="set TrainConfig.norm_reward on the chosen configs (MLP models)")
     args = ap.parse_args()
     opts = json.loads(args.engine_opts) if args.engine_opts else None
     for name in args.configs.split(","):
         res = run(name, args.updates, args.warmup, args.engine, args.device, args.dp_world1, opts,
-                  args.bootstrap_on_timeout, args.norm_obs)
+                  args.bootstrap_on_timeout, args.norm_obs, args.norm_reward)
         os.write(out_fd, (json.dumps(res) + "\n").encode())
 
 
