@@ -46,6 +46,14 @@ def ppo_actor_loss(logp, logp_old, adv, entropy, clip_eps, ent_coef, beta=0.0):
     return pg + beta * kl - ent_coef * ent, pg, kl, ent, clipfrac
 
 
+def approx_kl(logp, logp_old):
+    """``mean(expm1(x) - x)`` with ``x = logp - logp_old``: the ``(r - 1) - log r`` estimator of KL(old || new) over
+    the sampled actions, never negative; ``expm1`` because ``(exp(x) - 1) - x`` cancels badly for small ``x``. The
+    early-stopping statistic of ``TrainConfig.target_kl``."""
+    x = logp - logp_old
+    return (torch.expm1(x) - x).mean()
+
+
 def value_loss(v, returns, v_old=None, clip_eps=None):
     if v_old is not None and clip_eps is not None:
         v_clip = v_old + torch.clamp(v - v_old, -clip_eps, clip_eps)

@@ -66,7 +66,9 @@ def parse_fault(spec):
     return int(r), int(it)
 
 # layout of the device statistics buffer; slots 0..6 are written directly by the fused loss kernel
-STAT_KEYS = ("pg", "kl", "entropy", "crit_loss", "clipfrac", "act_loss", "ratio", "ev_before", "ev_after")
+# (9, 10: the approximate KL of the last evaluated PPO minibatch and the steps applied in the update, target_kl)
+STAT_KEYS = ("pg", "kl", "entropy", "crit_loss", "clipfrac", "act_loss", "ratio", "ev_before", "ev_after",
+             "approx_kl", "ppo_steps")
 LOG_KEYS = ("act_loss", "crit_loss", "kl", "entropy", "ev_before", "ev_after", "clipfrac")
 
 
@@ -140,6 +142,8 @@ class ActorCriticTrainer:
             self._check_norm_obs()
         if cfg.norm_reward:
             self._check_norm_reward()
+        if cfg.target_kl is not None:
+            self._check_target_kl()
         if dp is not None:
             dp.broadcast_params(self.flat)
             if cfg.grad_bucket_dtype == "bf16" and dp.compress is None:
@@ -228,6 +232,21 @@ class ActorCriticTrainer:
         self.stats_buf = torch.zeros(16, dtype=torch.float32, device=dev)
         self.stats = {k: self.stats_buf[i] for i, k in enumerate(STAT_KEYS)}
         self.adv_buf = torch.zeros(T * N, dtype=torch.float32, device=dev)
+        # PPO early stopping on the approximate KL (target_kl), decided on the device: [go (1 = armed, 0 = stopped),
+        # steps applied in this update, the step that stopped it (INT32_MAX: none; native engine)], re-armed by every update's first minibatch; the threshold is one float32
+        # computed here; kl_trace[j] = approx_kl in front of minibatch step j, -1 where the update had stopped (kept
+        # for every PPO run, like the approx_kl statistic). Transient within an update: not in checkpoints.
+        self._kl_state = self._kl_trace = None
+        self._kl_thr = 0.0
+        if cfg.algo == "ppo":
+            self._kl_trace = torch.full((cfg.ppo_epochs * cfg.ppo_minibatches,), -1.0, dtype=torch.float32, device=dev)
+        if cfg.target_kl is not None:
+            self._kl_state = torch.tensor([1, 0, 2 ** 31 - 1], dtype=torch.int32, device=dev)
+            self._kl_armed = self._kl_state.clone()   # torch engine: copied over the state as an update begins
+            self._kl_thr = float(torch.tensor(1.5, dtype=torch.float32) *
+                                 torch.tensor(float(cfg.target_kl), dtype=torch.float32))
+            for opt in self.opts.values():
+                opt.set_gate(self._kl_state[0:1])
         self.iteration = 0
         self.env_steps = 0
         self.graph = None
@@ -279,6 +298,20 @@ class ActorCriticTrainer:
             raise ValueError(f"norm_reward=True with algo={self.cfg.algo!r}: the reference-parity trainers (a3c, "
                              "basic_ac) keep the reference's raw rewards; use a2c or ppo")
 
+    def _check_target_kl(self):
+        """``target_kl`` covers PPO on one rank: the torch engine (any model) and the native MLP engine."""
+        from ..models.policy import CNNActorCritic
+        if self.cfg.algo != "ppo":
+            raise ValueError(f"target_kl with algo={self.cfg.algo!r}: early stopping ends the remaining minibatch "
+                             "steps of a PPO update; use algo='ppo'")
+        if self.dp is not None:
+            raise ValueError("target_kl under data parallelism: every rank must take the same stop decision, so the "
+                             "approximate KL has to travel in the gradient all-reduce, which is not built yet; run on "
+                             "one rank or leave target_kl=None")
+        if self.cfg.engine == "native" and isinstance(self.model, CNNActorCritic):
+            raise ValueError("target_kl with engine='native' and a CNN model: the native CNN engine has no early-stop "
+                             "gate; use engine='auto' (falls back to the torch engine) or 'torch'")
+
     def _scale_rewards(self):
         """After the rollout wrote the raw rewards, before any bootstrap term: scan, merge (under DP one small
         collective, between rollout and returns) and scale in place."""
@@ -309,8 +342,8 @@ class ActorCriticTrainer:
         if self.cfg.bootstrap_on_timeout and eng == "native":
             raise ValueError("bootstrap_on_timeout needs the terminal observation of truncated episodes, which the "
                              "native env/rollout kernels do not keep: use engine='torch'")
-        if eng == "torch" or self.cfg.bootstrap_on_timeout or self.device.type != "cuda" or \
-                not isinstance(self.model, CNNActorCritic):
+        if eng == "torch" or self.cfg.bootstrap_on_timeout or self.cfg.target_kl is not None or \
+                self.device.type != "cuda" or not isinstance(self.model, CNNActorCritic):
             if eng == "native":
                 raise ValueError("engine='native' needs a CNN model on a GPU")
             return False
@@ -614,6 +647,7 @@ class ActorCriticTrainer:
     def _loss(self, obs, actions, logp_old, adv, ret, v_old=None):
         cfg = self.cfg
         logp, ent, v = self.model.evaluate(obs, actions)
+        self._last_logp = logp.detach()   # the approximate KL of this minibatch (_kl_rule) reads it
         if cfg.algo == "ppo":
             a_loss, pg, kl, entm, clipfrac = L.ppo_actor_loss(logp, logp_old, adv, ent, cfg.ppo_clip, self.ent_coef,
                                                               self.kl_coef)
@@ -684,6 +718,9 @@ class ActorCriticTrainer:
         if self._defer_allreduce:
             return
         if self._grad_sink is not None:   # async PS worker (a3c_gpu): push the gradient, pull the parameters
+            if self.cfg.target_kl is not None:
+                raise ValueError("target_kl with the async parameter-server gradient sink: the optimiser step it "
+                                 "would gate runs on the server")
             self._comm(self._grad_sink)
             self._after_pull()
             return
@@ -767,11 +804,12 @@ class ActorCriticTrainer:
         v_old = st.flat("values")
         adv = self._pre_learn_stats(ret, adv, v_old)
         if cfg.algo == "ppo":
-            for sel in self._minibatches(obs.shape[0]):
+            for j, sel in enumerate(self._minibatches(obs.shape[0])):
                 self.flat.zero_grad()
                 total, a_loss, c_loss, kl, ent, cf = self._loss(obs[sel], actions[sel], logp_old[sel], adv[sel],
                                                                 ret[sel], v_old[sel])
                 total.backward()
+                self._kl_rule(j, L.approx_kl(self._last_logp, logp_old[sel]))
                 self._apply_grads()
         else:
             self.flat.zero_grad()
@@ -786,6 +824,28 @@ class ActorCriticTrainer:
         self.update_counter += 1
         if self.lr_ctrl is not None or cfg.kl_coef > 0:
             self._post_update_kl(obs, actions, logp_old, ret)
+
+    @torch.no_grad()
+    def _kl_rule(self, j, akl):
+        """Torch engine, in front of minibatch step ``j`` of a PPO update: publishes the minibatch's approximate KL
+        and, with ``target_kl``, takes the stop decision on the device -- the optimisers are gated on ``go``
+        (``FusedAdam.set_gate``), so once it is 0 this step and every remaining one apply nothing. No host read: the
+        same ops run eagerly and inside a captured update."""
+        akl = akl.to(torch.float32)
+        st = self._kl_state
+        if st is None:
+            self.stats["approx_kl"].copy_(akl)
+            self._kl_trace[j].copy_(akl)
+            return
+        if j == 0:   # the update starts armed, with no step applied
+            st.copy_(self._kl_armed)
+        armed = st[0] != 0
+        stop = armed & (akl > self._kl_thr)   # strict; NaN compares false
+        self.stats["approx_kl"].copy_(torch.where(armed, akl, self.stats["approx_kl"]))
+        self._kl_trace[j].copy_(torch.where(armed, akl, torch.full_like(akl, -1.0)))
+        st[1] += (armed & ~stop).to(torch.int32)
+        st[0] *= (~stop).to(torch.int32)
+        self.stats["ppo_steps"].copy_(st[1].to(torch.float32))
 
     @torch.no_grad()
     def _post_update_kl(self, obs, actions, logp_old, ret):
@@ -841,13 +901,17 @@ class ActorCriticTrainer:
             self.lr_ctrl.update_(self.actor_opt.lr, kl)
 
     # ------------------------------------------------------------------ learning (native MLP engine)
-    def _mlp_step(self, eng, B, idx, obs, actions, logp_old, adv, ret, v_old, perm=None, bump=None):
+    def _mlp_step(self, eng, B, idx, obs, actions, logp_old, adv, ret, v_old, perm=None, bump=None, j=0):
         cfg = self.cfg
         ppo = cfg.algo == "ppo"
+        # PPO step j: the weight-gradient launch publishes the minibatch's approximate KL (statistics slots 9, 10 and
+        # kl_trace[j]); with target_kl it also takes the stop decision, and both launches are no-ops once stopped
+        kl = dict(kl_stat=self.stats_buf[9:11], kl_trace=self._kl_trace[j:j + 1], go=self._kl_state,
+                  kl_thr=self._kl_thr, kl_step=j) if ppo else {}
         used = eng.train(obs, actions, logp_old, adv, ret, self.ent_coef, self.kl_coef, B, idx=idx, perm=perm, bump=bump,
                          v_old=v_old if ppo else None, vf_coef=1.0, ppo=ppo, ppo_clip=cfg.ppo_clip if ppo else 0.0,
                          v_clip=(cfg.ppo_value_clip or 0.0) if ppo else 0.0, stats=self.stats_buf,
-                         clips=(cfg.clip_value, cfg.critic_clip_value), want_parts=self.dp is None)
+                         clips=(cfg.clip_value, cfg.critic_clip_value), want_parts=self.dp is None, **kl)
         for t, g in enumerate(("actor", "critic")):
             self.opts[g].ext_parts = eng.parts[t] if used else None
         self._apply_grads()
@@ -885,19 +949,30 @@ class ActorCriticTrainer:
             for ep in range(cfg.ppo_epochs):
                 # the epoch's rows in minibatch order (the keyed permutation, one gather launch): the train launches
                 # read contiguous rows, with no index or permutation round trip ahead of their input tiles
+                # target_kl: the update's first gather also arms the stop flag (go = 1, steps = 0) and, where the
+                # weight-gradient launches accumulate, clears the slab of what a stopped update's last launch added
+                arm = self._kl_state if ep == 0 else None
+                clear = self.flat.grad if (arm is not None and eng.wgrad_nsplit(mb) > 1) else None
                 _native.require().mlp_epoch_gather(lobs, actions, logp_old, adv, ret, v_old, g["obs"], g["act"],
-                                                   g["logp"], g["adv"], g["ret"], g["v"], uc, ep, self.policy_seed)
+                                                   g["logp"], g["adv"], g["ret"], g["v"], uc, ep, self.policy_seed,
+                                                   arm, clear)
                 for k in range(cfg.ppo_minibatches):
                     last = ep == cfg.ppo_epochs - 1 and k == cfg.ppo_minibatches - 1
                     self._t_off = ep * cfg.ppo_minibatches + k if offsets else None
                     sl = slice(k * mb, (k + 1) * mb)
                     # the last minibatch's weight-gradient launch advances the update counter (no extra launch)
                     self._mlp_step(eng, mb, None, g["obs"][sl], g["act"][sl], g["logp"][sl], g["adv"][sl],
-                                   g["ret"][sl], g["v"][sl], bump=self.update_counter if last else None)
+                                   g["ret"][sl], g["v"][sl], bump=self.update_counter if last else None,
+                                   j=ep * cfg.ppo_minibatches + k)
             self._t_off = None
             if self._t_offs_used:
                 assert self._t_offs_used == cfg.ppo_epochs * cfg.ppo_minibatches
-                self._group_step.advance(self._t_offs_used)
+                if self._kl_state is None:
+                    self._group_step.advance(self._t_offs_used)
+                else:
+                    # early stopping: the applied steps are the first `steps` of the sequence (a stopped update applies
+                    # nothing more), so their offsets were right; the counters move by the device's count
+                    self._group_step.advance(self.stats["ppo_steps"])
         else:
             self._mlp_step(eng, B, None, lobs, actions, logp_old, adv, ret, v_old)
             self.update_counter += 1
@@ -1389,6 +1464,11 @@ class ActorCriticTrainer:
                     avg_rew=avg_rew, print_tog=print_tog, act_lr=self.actor_opt.get_lr(), avg_ent=s["entropy"],
                     worker_id=self.worker_id, ev_before=s["ev_before"], ev_after=s["ev_after"])
         s.update(avg_rew=avg_rew, episodes=n_ep, ep_len=ep_len)
+        if self.cfg.target_kl is not None:
+            # early stopping: the approximate KL of the last minibatch evaluated (the one that stopped the update, if
+            # any did) and the optimiser steps the update applied, for the metrics stream only
+            s["approx_kl"] = vals[STAT_KEYS.index("approx_kl")]
+            s["ppo_steps"] = int(vals[STAT_KEYS.index("ppo_steps")])
         if self._kl_deferred():
             # DP + global advantage normalisation: this row's kl is rank 0's local post-update KL and act_lr the value
             # before the KL-adaptive rule, which settles inside the NEXT update's moments all-reduce (_kl_deferred);

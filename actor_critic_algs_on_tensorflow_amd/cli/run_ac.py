@@ -36,6 +36,9 @@ def build_parser():
                    help="running observation normalisation (TrainConfig.norm_obs; --algo a2c|ppo, MLP models)")
     p.add_argument("--norm-reward", action="store_true",
                    help="running return-based reward scaling (TrainConfig.norm_reward; --algo a2c|ppo, MLP models)")
+    p.add_argument("--target-kl", default=None, type=float,
+                   help="PPO early stopping: skip an update's remaining minibatch steps once the approximate KL "
+                        "exceeds 1.5 x this (TrainConfig.target_kl; --algo ppo, one device)")
     return p
 
 
@@ -57,6 +60,8 @@ def main(argv=None):
         kw["norm_obs"] = True
     if a.norm_reward:
         kw["norm_reward"] = True
+    if a.target_kl is not None:
+        kw["target_kl"] = a.target_kl
     cfg = preset(name, **kw)
     res = train(cfg)
     print("done: %d iterations, %d env steps, %.1f env-steps/s" % (res.iterations, res.env_steps,

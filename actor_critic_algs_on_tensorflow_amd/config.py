@@ -125,6 +125,12 @@ class TrainConfig:
     ppo_minibatches: int = 4
     ppo_clip: float = 0.1
     ppo_value_clip: float | None = None
+    # early stopping on the approximate KL: before each minibatch step, approx_kl = mean(expm1(x) - x) with
+    # x = logp - logp_old at the current parameters; once approx_kl > 1.5 * target_kl that step and every remaining
+    # step of the update are not applied (parameters, moments and Adam step counts untouched). Decided on the device
+    # (the captured update issues nothing from the host). PPO on the torch engine and the native MLP engine; no data
+    # parallelism yet. None = off
+    target_kl: float | None = None
     # -- execution -----------------------------------------------------------------------------------------------
     dtype: str = "bf16"               # compute dtype of the GPU engine (fp32 masters always)
     engine: str = "auto"              # auto | native (hand-written HIP engine) | torch (autograd reference)
@@ -193,6 +199,15 @@ class TrainConfig:
                                  "is for the MLP models")
             if not self.reward_clip > 0:
                 raise ValueError(f"TrainConfig.reward_clip={self.reward_clip}: must be > 0")
+        if self.target_kl is not None:
+            if not float(self.target_kl) > 0:
+                raise ValueError(f"TrainConfig.target_kl={self.target_kl}: must be > 0 (None = no early stopping)")
+            if self.algo != "ppo":
+                raise ValueError(f"TrainConfig.target_kl with algo={self.algo!r}: early stopping ends the remaining "
+                                 "minibatch steps of a PPO update; use algo='ppo'")
+            if self.engine == "native" and self.model == "cnn":
+                raise ValueError("TrainConfig.target_kl with engine='native' and model='cnn': the native CNN engine "
+                                 "has no early-stop gate; use engine='auto' or 'torch'")
         if self.look_ahead is not None and int(self.look_ahead) < 1:
             raise ValueError(f"TrainConfig.look_ahead={self.look_ahead}: must be >= 1 (None = the whole rollout)")
 

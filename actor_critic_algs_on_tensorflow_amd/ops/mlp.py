@@ -234,7 +234,7 @@ class MLPEngine:
     def _fwd(self, mode, obs, B, tw_base=0, ntw=2, desc_B=None, idx=None, perm=None, tg=None, env_ids=None, key_shift=0,
              seed=0, act_out=None, logp_out=None, ent_out=None, v_out=None, act_in=None, logp_old=None, adv=None,
              ret=None, v_old=None, ent_coef=None, kl_coef=None, vf_coef=1.0, ppo_clip=0.0, v_clip=0.0, ppo=False,
-             stamps=None):
+             stamps=None, go=None):
         ops = _native.require()
         desc, _ = self.desc(desc_B)
         obs2 = obs.reshape(obs.shape[0], -1)
@@ -246,7 +246,7 @@ class MLPEngine:
                     act_in, logp_old, adv, ret, v_old, ent_coef, kl_coef, float(vf_coef), float(ppo_clip),
                     float(v_clip or 0.0), bool(ppo), self.g_log_std if mode == 2 else None,
                     self.mstats if mode == 2 else None, self._mpart(B) if mode == 2 else None, stamps,
-                    self._hdescs[desc_B] if (mode == 2 and self.spec) else None, tables, nclip)
+                    self._hdescs[desc_B] if (mode == 2 and self.spec) else None, tables, nclip, go)
 
     # ------------------------------------------------------------------------------------------- API
     def policy_step(self, obs, act_out, logp_out, ent_out, v_out, tg, env_ids, key_shift, seed):
@@ -264,26 +264,42 @@ class MLPEngine:
 
     def train(self, obs, actions, logp_old, adv, ret, ent_coef, kl_coef, B, idx=None, v_old=None, vf_coef=1.0,
               ppo=False, ppo_clip=0.0, v_clip=0.0, stats=None, clips=(None, None), want_parts=True, perm=None,
-              bump=None, stamps=None):
+              bump=None, stamps=None, kl_stat=None, go=None, kl_thr=0.0, kl_trace=None, kl_step=0):
         """One learner (mini)batch: rows ``idx`` / ``perm`` = (update_counter, epoch, offset, n, seed) -- the rows
         ``prp(offset + r)`` of the keyed permutation of ``[0, n)`` (envs/rng.py), computed in-kernel -- or the first
         ``B`` rows of the rollout -> gradients in the slab, statistics into ``stats[0:7]``, sums of squares into
         :attr:`parts` (when ``want_parts``). ``bump``: an int64 counter the weight-gradient launch advances by one
-        (the PPO update counter, after the update's last minibatch -- no separate launch)."""
+        (the PPO update counter, after the update's last minibatch -- no separate launch).
+
+        PPO early stopping (``TrainConfig.target_kl``): ``kl_stat`` (fp32 [2]) receives the minibatch's ``approx_kl =
+        mean(expm1(logp - logp_old) - (logp - logp_old))`` and, with ``go``, the steps applied so far; ``go`` (int32
+        [flag, steps, stop_at]): while the flag is 1, ``approx_kl > kl_thr`` stores 0 into it and ``kl_step`` (this
+        step's index within the update) into ``stop_at``, otherwise ``steps`` goes up by one; while it is 0 both
+        launches write nothing but ``kl_trace = -1`` (and the ``bump``): the train launch and the bookkeeping read the
+        flag, the weight-gradient items ``stop_at < kl_step``. ``kl_trace`` (one
+        fp32 slot) receives ``approx_kl``. The caller gates the optimiser launch on the same flag
+        (``FusedAdam.set_gate``) and re-arms it (``mlp_epoch_gather``)."""
         ops = _native.require()
         self._fwd(2, obs, B, 0, 2, desc_B=B, idx=idx, perm=perm, act_in=actions, logp_old=logp_old, adv=adv, ret=ret,
                   v_old=v_old, ent_coef=ent_coef, kl_coef=kl_coef, vf_coef=vf_coef, ppo_clip=ppo_clip,
-                  v_clip=v_clip, ppo=ppo, stamps=stamps)
+                  v_clip=v_clip, ppo=ppo, stamps=stamps, go=go)
         nrt = (B + BM - 1) // BM
-        nsplit = max(1, min(16, nrt // 128))
+        nsplit = self.wgrad_nsplit(B)
         self.last_stores_all = nsplit == 1   # every gradient element stored (no atomics): no zeroing needed after use
         use_parts = want_parts and nsplit == 1
         st = stats if stats is not None else self._dummy_stats
         items = self.wgrad_items(B, use_parts, clips)
         ls_part = self.parts[0][self.items[0]:self.items[0] + 1] if (use_parts and self.g_log_std is not None) else None
         ops.mlp_wgrad(items, nrt, nsplit, self.g_log_std, self.A, ls_part, float(clips[0] or -1.0), st, ent_coef,
-                      kl_coef, self._mpart(B), nrt, bump)
+                      kl_coef, self._mpart(B), nrt, bump, kl_stat, go, float(kl_thr), kl_trace,
+                      int(kl_step))
         return use_parts
+
+    @staticmethod
+    def wgrad_nsplit(B):
+        """Row-tile splits of the weight-gradient launch for a batch of ``B`` rows: above 1 (from 4096 rows) the splits
+        ADD their tiles into the gradient slab instead of storing them."""
+        return max(1, min(16, (B + BM - 1) // BM // 128))
 
     def wgrad_items(self, B, parts=True, clips=(None, None)):
         """Item table of the weight-gradient launch (``mlp.hip`` mlp_wgrad_kernel, 8 int64 per 16 x 16 tile of every

@@ -16,6 +16,8 @@ same kernel writes a bf16 shadow copy of the parameters for the MFMA forward/bac
 """
 from __future__ import annotations
 
+import weakref
+
 import torch
 
 from .. import _native
@@ -100,6 +102,9 @@ class FusedAdam:
         self.gate = None
         # optional bf16 gradient read instead of g (bind_grad16: the all-reduced bf16 DP bucket, no cast back)
         self.g16 = None
+        # every FusedGroupStep built over this optimiser (each keeps its own copy of the table rows: set_gate
+        # refreshes them all); weak references, a discarded group step is not kept alive
+        self._groups = []
 
     def bind_grad(self, grad_slab):
         """Read gradients from this group's segment of another slab (lag-1 DP reads the all-reduced copy)."""
@@ -127,11 +132,20 @@ class FusedAdam:
         self._frag_table = self._table()
 
     def set_gate(self, gate):
-        """Device int32 flag (``optim.hip`` OptSeg::gate): while it is 0 the native update is skipped -- parameters,
-        moments and the Adam step count stay as they are (lag-1 data parallelism before its first all-reduced
-        gradient, ``trainer.py`` _update_body_lag1). ``None`` removes it."""
+        """Device int32 flag (``optim.hip`` OptSeg::gate): while it is 0 the update is skipped -- parameters, moments,
+        the Adam step count, shadows and fragment copies stay as they are (lag-1 data parallelism before its first
+        all-reduced gradient, ``trainer.py`` _update_body_lag1; PPO early stopping, ``TrainConfig.target_kl``).
+        ``None`` removes it. The gate may be set at any time: both tables that carry it are rebuilt here, this
+        optimiser's own and the ``_trans`` table of every :class:`FusedGroupStep` built over it (which copies the rows at
+        construction -- usually during the capture warm-up, before a gate exists). On a GPU the kernels read the flag
+        (nothing comes back to the host, so a captured update keeps working); the torch step of the CPU oracle reads
+        it on the host."""
         self.gate = gate
         self._frag_table = self._table()
+        for ref in self._groups:
+            gs = ref()
+            if gs is not None:
+                gs.rebuild_trans()
 
     def table_rows(self):
         """Rows (offset, K, N, code, ptr) of this optimiser's copy / gate table (``optim.hip`` opt_load_trans)."""
@@ -281,7 +295,15 @@ class FusedGroupStep:
             for k, o in enumerate(self.opts):
                 if copies[k]:
                     self._items[k] = self.item_table(o, copies[k])
+        for o in self.opts:
+            o._groups = [r for r in o._groups if r() is not None] + [weakref.ref(self)]
+        self.rebuild_trans()
+
+    def rebuild_trans(self):
+        """The launch's copy / gate table from the optimisers' current rows (``FusedAdam.table_rows``); called again by
+        ``FusedAdam.set_gate``, so a gate set after construction is honoured."""
         own = [o.table_rows() for o in self.opts]
+        self._trans = None
         if any(own):
             t = torch.zeros(len(self.opts), self.MAXT, 5, dtype=torch.int64)
             for k, rows in enumerate(own):
@@ -376,10 +398,10 @@ class FusedGroupStep:
 
     def advance(self, n):
         """After ``n`` steps taken with ``t_off`` = 0 .. n-1: the Adam step counters move by ``n`` (one device add
-        per group)."""
+        per group). ``n``: a number, or a device fp32 scalar holding the count of steps a gate let through."""
         if self.adam:
             for o in self.opts:
-                o.t.add_(float(n))
+                o.t.add_(n if torch.is_tensor(n) else float(n))
 
 
 def frag_order(W, K, N):

@@ -975,7 +975,8 @@ void mlp_fwd(Tensor desc, int64_t tw_base, int64_t ntw, int64_t mode, int64_t ld
              c10::optional<Tensor> v_old, c10::optional<Tensor> ent_coef, c10::optional<Tensor> kl_coef,
              double vf_coef, double ppo_clip, double v_clip, bool ppo, c10::optional<Tensor> g_log_std,
              c10::optional<Tensor> mstats, c10::optional<Tensor> mpart, c10::optional<Tensor> stamps,
-             c10::optional<Tensor> hdesc, c10::optional<Tensor> norm_tables, double norm_clip) {
+             c10::optional<Tensor> hdesc, c10::optional<Tensor> norm_tables, double norm_clip,
+             c10::optional<Tensor> go) {
   need(desc, at::kLong, "desc");
   TORCH_CHECK(desc.numel() * 8 >= (int64_t)(2 * sizeof(aca::MlpTower)), "mlp_fwd: desc too small");
   TORCH_CHECK(obs.is_cuda() && obs.scalar_type() == at::kFloat && obs.dim() == 2 && obs.stride(1) == 1,
@@ -1078,6 +1079,9 @@ void mlp_fwd(Tensor desc, int64_t tw_base, int64_t ntw, int64_t mode, int64_t ld
     a.norm_istd = a.norm_mean + obs.size(1);
     a.norm_clip = (float)norm_clip;
   }
+  // PPO early-stop flag (target_kl): train launches only
+  a.go = copt<int32_t>(go, at::kInt, "go");
+  if (a.go) TORCH_CHECK(mode == 2 && go->numel() >= 1, "mlp_fwd: go is one int32 flag of a train launch");
   check(aca_mlp_fwd(&a, (int)ntw, (size_t)lds, spec, cur_stream(obs)), "mlp_fwd");
 }
 
@@ -1091,7 +1095,9 @@ void mlp_tshadow(Tensor desc, int64_t ntw, int64_t total) {
 // items: device int64 [nitems, 8] (ops/mlp.py MLPEngine.wgrad_items); nrt: 16-row tiles of the batch
 void mlp_wgrad(Tensor items, int64_t nrt, int64_t nsplit, c10::optional<Tensor> g_log_std, int64_t A,
                c10::optional<Tensor> ls_part, double ls_clip, c10::optional<Tensor> stats, Tensor ent_coef,
-               Tensor kl_coef, Tensor mpart, int64_t mpart_rows, c10::optional<Tensor> bump) {
+               Tensor kl_coef, Tensor mpart, int64_t mpart_rows, c10::optional<Tensor> bump,
+               c10::optional<Tensor> kl_stat, c10::optional<Tensor> go, double kl_thr,
+               c10::optional<Tensor> kl_trace, int64_t kl_step) {
   need(items, at::kLong, "items");
   TORCH_CHECK(items.dim() == 2 && items.size(1) == 8 && items.size(0) >= 1, "mlp_wgrad: items must be [n, 8]");
   aca::WgradArgs a{};
@@ -1116,13 +1122,28 @@ void mlp_wgrad(Tensor items, int64_t nrt, int64_t nsplit, c10::optional<Tensor> 
   a.kl_coef = kl_coef.data_ptr<float>();
   a.mpart = mpart.data_ptr<float>();
   a.mpart_rows = (int)mpart_rows;
+  // PPO early stopping (target_kl): kl_stat = [approx_kl, steps applied], go = [flag, steps, stop_at], kl_trace = one
+  // slot, kl_step = this minibatch step's index within the update
+  a.kl_stat = const_cast<float*>(copt<float>(kl_stat, at::kFloat, "kl_stat"));
+  if (a.kl_stat) TORCH_CHECK(kl_stat->numel() >= 2, "mlp_wgrad: kl_stat holds approx_kl and the step count");
+  if (has(go)) {
+    need(*go, at::kInt, "go");
+    TORCH_CHECK(go->numel() >= 3 && kl_step >= 0, "mlp_wgrad: go must be int32 [flag, steps, stop_at], kl_step >= 0");
+    a.go = go->data_ptr<int32_t>();
+    a.steps = a.go + 1;
+  }
+  a.kl_thr = (float)kl_thr;
+  a.kl_step = (int)kl_step;
+  a.kl_trace = const_cast<float*>(copt<float>(kl_trace, at::kFloat, "kl_trace"));
+  if (a.kl_trace) TORCH_CHECK(kl_trace->numel() >= 1, "mlp_wgrad: kl_trace is one slot");
   check(aca_mlp_wgrad(&a, cur_stream(items)), "mlp_wgrad");
 }
 
 // PPO epoch gather for the MLP engine: out rows i = in rows prp(i) (keyed by the device update counter uc, epoch ep)
 void mlp_epoch_gather(Tensor obs, Tensor act, Tensor logp, Tensor adv, Tensor ret, c10::optional<Tensor> v,
                       Tensor o_obs, Tensor o_act, Tensor o_logp, Tensor o_adv, Tensor o_ret, c10::optional<Tensor> o_v,
-                      Tensor uc, int64_t ep, int64_t seed) {
+                      Tensor uc, int64_t ep, int64_t seed, c10::optional<Tensor> arm,
+                      c10::optional<Tensor> clear) {
   TORCH_CHECK(obs.is_cuda() && obs.scalar_type() == at::kFloat && obs.dim() == 2 && obs.stride(1) == 1,
               "mlp_epoch_gather: obs must be fp32 [n, D] with unit column stride");
   const int64_t n = obs.size(0), D = obs.size(1);
@@ -1159,6 +1180,18 @@ void mlp_epoch_gather(Tensor obs, Tensor act, Tensor logp, Tensor adv, Tensor re
   a.uc = uc.data_ptr<int64_t>();
   a.ep = (int)ep;
   a.seed = (uint32_t)seed;
+  // PPO early stopping (target_kl): arm = int32 [flag, steps, stop_at] set to [1, 0, INT32_MAX]; clear = a gradient
+  // slab to zero
+  if (has(arm)) {
+    need(*arm, at::kInt, "arm");
+    TORCH_CHECK(arm->numel() >= 3, "mlp_epoch_gather: arm must be int32 [flag, steps, stop_at]");
+    a.arm = arm->data_ptr<int32_t>();
+  }
+  if (has(clear)) {
+    need(*clear, at::kFloat, "clear");
+    a.clear = clear->data_ptr<float>();
+    a.clear_n = clear->numel();
+  }
   check(aca_mlp_epoch_gather(&a, cur_stream(obs)), "mlp_epoch_gather");
 }
 
@@ -2178,11 +2211,13 @@ TORCH_LIBRARY(acamd, m) {
         "Tensor? act_out, Tensor? logp_out, Tensor? ent_out, Tensor? v_out, Tensor? act_in, Tensor? logp_old, "
         "Tensor? adv, Tensor? ret, Tensor? v_old, Tensor? ent_coef, Tensor? kl_coef, float vf_coef, float ppo_clip, "
         "float v_clip, bool ppo, Tensor? g_log_std, Tensor? mstats, Tensor? mpart=None, Tensor? stamps=None, Tensor? hdesc=None, "
-        "Tensor? norm_tables=None, float norm_clip=0.0) -> ()");
+        "Tensor? norm_tables=None, float norm_clip=0.0, Tensor? go=None) -> ()");
   m.def("mlp_wgrad(Tensor items, int nrt, int nsplit, Tensor? g_log_std, int A, Tensor? ls_part, float ls_clip, "
-        "Tensor? stats, Tensor ent_coef, Tensor kl_coef, Tensor mpart, int mpart_rows, Tensor? bump) -> ()");
+        "Tensor? stats, Tensor ent_coef, Tensor kl_coef, Tensor mpart, int mpart_rows, Tensor? bump, "
+        "Tensor? kl_stat=None, Tensor? go=None, float kl_thr=0.0, Tensor? kl_trace=None, int kl_step=0) -> ()");
   m.def("mlp_epoch_gather(Tensor obs, Tensor act, Tensor logp, Tensor adv, Tensor ret, Tensor? v, Tensor o_obs, "
-        "Tensor o_act, Tensor o_logp, Tensor o_adv, Tensor o_ret, Tensor? o_v, Tensor uc, int ep, int seed) -> ()");
+        "Tensor o_act, Tensor o_logp, Tensor o_adv, Tensor o_ret, Tensor? o_v, Tensor uc, int ep, int seed, "
+        "Tensor? arm=None, Tensor? clear=None) -> ()");
   m.def("mlp_rollout(Tensor desc, int lds, Tensor obs, Tensor act, Tensor logp, Tensor ent, Tensor reward, "
         "Tensor done, Tensor truncated, Tensor log_std, Tensor ac_scale, int key_shift, int policy_seed, "
         "Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, Tensor lin_A, "

@@ -527,6 +527,25 @@ __device__ __forceinline__ void spec_load(CriticRegs<NG0>& R, const MlpTower& T,
   // (g1, W1's data-gradient set: issued under layer 1's MFMAs, wset_fwd_side)
 }
 
+// The row term of the approximate KL (TrainConfig.target_kl): expm1(x) - x, x = logp - logp_old, r = expf(x) (which
+// every PPO head has). |x| < 1: x^2 (1/2! + x/3! + ... + x^9/11!), the series without its first two terms (truncation
+// 2/12! = 4e-9 of the result; exactly 0 at x = 0, no cancellation); otherwise (r - 1) - x, whose result is >= 0.36
+// there, so the rounding of r costs a few ulp of it. The library expm1f gives the same to rounding; traced in one
+// session against this form it made the train launch 0.12 .. 0.16 us longer (profiles/target_kl.txt, session 3).
+__device__ __forceinline__ float kl_term(float x, float r) {
+  float p = 1.f / 39916800.f;
+  p = fmaf(p, x, 1.f / 3628800.f);
+  p = fmaf(p, x, 1.f / 362880.f);
+  p = fmaf(p, x, 1.f / 40320.f);
+  p = fmaf(p, x, 1.f / 5040.f);
+  p = fmaf(p, x, 1.f / 720.f);
+  p = fmaf(p, x, 1.f / 120.f);
+  p = fmaf(p, x, 1.f / 24.f);
+  p = fmaf(p, x, 1.f / 6.f);
+  p = fmaf(p, x, 0.5f);
+  return fabsf(x) < 1.f ? x * x * p : (r - 1.f) - x;   // (NaN takes the second form and stays NaN)
+}
+
 // one tower of mlp_fwd_kernel. SPEC 0: any tower (t at run time, layer loops over the device descriptor); SPEC > 0:
 // tower TW of the reference shapes in train mode, weights from registers.
 template <int SPEC, int TW>
@@ -892,6 +911,7 @@ __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* 
         st[0] = -fminf(s1, s2);
         st[4] = fabsf(ratio - 1.f) > a.ppo_clip ? 1.f : 0.f;
         st[6] = ratio;
+        st[7] = kl_term(lp - lo, ratio);   // approx_kl term (target_kl): expm1(x) - x
       } else {
         dsurr = adv;
         st[0] = -adv * lp;
@@ -1015,6 +1035,7 @@ __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* 
           st[0] = -fminf(s1, s2);
           st[4] = fabsf(ratio - 1.f) > a.ppo_clip ? 1.f : 0.f;
           st[6] = ratio;
+          st[7] = kl_term(lp - lo, ratio);
         } else {
           dsurr = adv;
           st[0] = -adv * lp;
@@ -1066,6 +1087,7 @@ __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* 
           st[0] = -fminf(s1, s2);
           st[4] = fabsf(ratio - 1.f) > a.ppo_clip ? 1.f : 0.f;
           st[6] = ratio;
+          st[7] = kl_term(lpa - lo, ratio);
         } else {
           dsurr = adv;
           st[0] = -adv * lpa;
@@ -1202,6 +1224,9 @@ template <int SPEC>
 __global__ void __launch_bounds__(MLP_THREADS) mlp_fwd_kernel(MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // 16-byte base: the b128 LDS reads stay aligned
   __shared__ MlpShared S;
+  // PPO early stop (target_kl): a stopped update's remaining launches are no-ops -- uniform over the launch (the flag
+  // was stored by an earlier launch), before any store or barrier
+  if (a.go && *a.go == 0) return;
   const int t = blockIdx.y + a.tw_base;
   if constexpr (SPEC == 0) {
     mlp_tower<0, -1>(a, t, sm, S);
@@ -1235,6 +1260,16 @@ __global__ void __launch_bounds__(256) mlp_wgrad_kernel(WgradArgs a) {
     // order (deterministic) -- the loss statistics published and the log-std gradient finished with its sum of
     // squares in its own slot -- and the update counter advanced. Every load is issued up front (one round trip).
     if (wave != 0) return;
+    // PPO early stop (target_kl): this workgroup is the flag's only writer on the device, so what it reads here was
+    // stored by an earlier launch. Stopped: the train launch returned at entry and the partial rows are the stopping
+    // minibatch's -- nothing is published (its statistics stay), the trace slot says "skipped", the counter still moves.
+    if (a.go && *a.go == 0) {
+      if (lane == 0) {
+        if (a.kl_trace) *a.kl_trace = -1.f;
+        if (a.bump) __hip_atomic_fetch_add(a.bump, (int64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      return;
+    }
     const float kl = *a.kl_coef, ec = *a.ent_coef;
     float v[MPART_W];
 #pragma unroll
@@ -1265,11 +1300,36 @@ __global__ void __launch_bounds__(256) mlp_wgrad_kernel(WgradArgs a) {
 #pragma unroll
         for (int k = 0; k < 7; ++k) a.stats[k] = m[k];
       }
+      // approx_kl of this minibatch (column 7 of the partial rows; 0 outside PPO) and the stop rule: strictly above
+      // the threshold (NaN compares false) closes the flag -- the optimiser launch behind this one is gated on it and
+      // every later launch of the update returns at entry -- otherwise one more step counts as applied
+      const float akl = v[7];
+      if (a.kl_stat) *a.kl_stat = akl;
+      if (a.kl_trace) *a.kl_trace = akl;
+      if (a.go) {
+        const bool stop = akl > a.kl_thr;
+        const int ns = *a.steps + (stop ? 0 : 1);
+        if (stop) {
+          a.go[2] = a.kl_step;   // the item workgroups of LATER launches return at entry (stop_at < their step)
+          *a.go = 0;
+        } else {
+          *a.steps = ns;
+        }
+        if (a.kl_stat) a.kl_stat[1] = (float)ns;   // steps applied so far, next to approx_kl in the statistics buffer
+      }
       // the train kernel (the counter's only reader in this minibatch) has finished: stream order
       if (a.bump) __hip_atomic_fetch_add(a.bump, (int64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     return;
   }
+  // PPO early stop: the item workgroups of launches BEHIND the one that stopped the update write nothing. They test
+  // stop_at (go[2]) < this launch's step, not the flag: the bookkeeping workgroup of this same launch may be closing
+  // the flag right now with plain stores, but the only value it can put into stop_at is this launch's own step, so the
+  // test reads the same in every wave whenever its load lands -- uniform over the launch, before any store or barrier.
+  // The launch that stops therefore writes its whole gradient; it is never applied (the optimiser launch behind is
+  // gated) and never survives: a storing launch overwrites every element, the accumulating path's slab is cleared when
+  // the next update arms (mlp_epoch_gather).
+  if (a.go && a.go[2] < a.kl_step) return;
   // XCD-grouped item order (common.h xcd_remap): each XCD takes one contiguous range of the item table, whose
   // neighbouring items (tiles of one layer) share their X / dP column blocks -- they meet in one L2
   const int bid = xcd_remap((int)blockIdx.x, (int)gridDim.x - 1);
@@ -1358,6 +1418,15 @@ __global__ void __launch_bounds__(256) mlp_wgrad_kernel(WgradArgs a) {
 // their input tiles. Actions are copied as 4-byte words (float components or the int32 index). One thread per row.
 __global__ void __launch_bounds__(256) mlp_epoch_gather_kernel(EpochGatherArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  // PPO early stop (target_kl), the update's first gather: the update starts armed with no step applied, and on the
+  // accumulating weight-gradient path the slab is cleared of whatever a stopped update's last launch added
+  if (a.arm && i == 0) {
+    a.arm[0] = 1;
+    a.arm[1] = 0;
+    a.arm[2] = 0x7fffffff;
+  }
+  if (a.clear)
+    for (int64_t e = i; e < a.clear_n; e += (int64_t)gridDim.x * blockDim.x) a.clear[e] = 0.f;
   if (i >= a.n) return;
   const int64_t src = prp_index((uint32_t)i, (uint32_t)a.n, minibatch_key(a.seed, *a.uc, a.ep));
   // every load of a chunk issued before its stores (a load -> store loop per column waits out one round trip per
@@ -1858,6 +1927,7 @@ extern "C" hipError_t aca_mlp_fwd(const MlpArgs* a, int ntw, size_t lds, int spe
   // observation tables: both or none, and never with a train launch (its rows are normalised already)
   if ((a->norm_mean != nullptr) != (a->norm_istd != nullptr) || (a->norm_mean && a->mode == 2))
     return hipErrorInvalidValue;
+  if (a->go && a->mode != 2) return hipErrorInvalidValue;   // the early-stop flag gates train launches only
   static bool attr = false;
   if (!attr) {
     const void* ks[4] = {reinterpret_cast<const void*>(&mlp_fwd_kernel<0>),
@@ -1885,6 +1955,7 @@ extern "C" hipError_t aca_mlp_wgrad(const WgradArgs* a, hipStream_t stream) {
   if (a->nrt <= 0) return hipSuccess;
   if (!a->items || a->nitems < 1 || a->nsplit < 1 || !a->mpart || !a->kl_coef || !a->ent_coef || a->A > MLP_MAXA)
     return hipErrorInvalidValue;
+  if (a->go && !a->steps) return hipErrorInvalidValue;   // the stop flag and its step count go together
   // + the bookkeeping workgroup (statistics, log-std gradient, update counter)
   mlp_wgrad_kernel<<<a->nitems * a->nsplit + 1, 256, 0, stream>>>(*a);
   return hipGetLastError();
@@ -1893,6 +1964,7 @@ extern "C" hipError_t aca_mlp_wgrad(const WgradArgs* a, hipStream_t stream) {
 extern "C" hipError_t aca_mlp_epoch_gather(const EpochGatherArgs* a, hipStream_t stream) {
   if (a->n <= 0) return hipSuccess;
   if (!a->uc || a->D < 1 || a->aw < 1) return hipErrorInvalidValue;
+  if (a->clear && a->clear_n < 0) return hipErrorInvalidValue;
   mlp_epoch_gather_kernel<<<(a->n + 255) / 256, 256, 0, stream>>>(*a);
   return hipGetLastError();
 }

@@ -60,6 +60,9 @@ struct MlpArgs {
   // that no existing field moves.
   const float* norm_mean; const float* norm_istd;   // [D] each
   float norm_clip;
+  // optional PPO early-stop flag (target_kl): while *go == 0 the launch returns at entry, before any store or barrier
+  // (uniform over the launch; the bookkeeping workgroup of an EARLIER weight-gradient launch stored it: stream order)
+  const int32_t* go;
 };
 
 struct WgradArgs {
@@ -72,6 +75,18 @@ struct WgradArgs {
   float* stats; const float* ent_coef; const float* kl_coef;
   const float* mpart; int mpart_rows;   // the train kernel's partial rows (reduced here in a fixed order)
   int64_t* bump;              // optional counter advanced once (PPO update counter after the update's last minibatch)
+  // optional PPO early stopping on the approximate KL (target_kl), all plain stores from one lane of the bookkeeping
+  // workgroup. kl_stat: the minibatch's approx_kl = mean(expm1(x) - x), x = logp - logp_old (statistics column 7 of
+  // the partial rows), published whenever given. go = int32 [flag, steps, stop_at] (+ kl_thr, kl_step): while the flag
+  // is 1 (armed) approx_kl > kl_thr stores stop_at = kl_step and flag = 0, else ++steps; while the flag is 0 (stopped)
+  // the bookkeeping workgroup publishes nothing but kl_trace = -1 (and still bumps). The item workgroups return at
+  // entry when stop_at < kl_step: an EARLIER launch stopped the update. They do not read the flag, which this very
+  // launch may be closing -- stop_at is either still above kl_step or exactly kl_step then, so every wave of the
+  // launch that stops takes the same branch and its gradient is written whole. kl_trace: this minibatch's trace slot.
+  float* kl_stat;
+  int32_t* go; int32_t* steps; float kl_thr;
+  float* kl_trace;
+  int kl_step;                // index of this launch's minibatch step within the update
 };
 
 // PPO epoch gather (mlp_epoch_gather_kernel): row i of the outputs = row prp(i) of the inputs
@@ -81,6 +96,12 @@ struct EpochGatherArgs {
   const uint32_t* act; const float* logp; const float* adv; const float* ret; const float* v;   // v optional
   float* o_obs; uint32_t* o_act; float* o_logp; float* o_adv; float* o_ret; float* o_v;
   const int64_t* uc; int ep; uint32_t seed;
+  // optional (target_kl, the update's first gather): arm[0] = 1 (go), arm[1] = 0 (steps applied), arm[2] = INT32_MAX
+  // (stop_at: no launch has stopped the update), one thread; and
+  // clear[0 : clear_n) = 0, the gradient slab where the weight-gradient launches accumulate (nsplit > 1): what a
+  // stopped update's last weight-gradient launch left there never reaches the next update
+  int32_t* arm;
+  float* clear; int64_t clear_n;
 };
 
 // Fused rollout of the MuJoCo-shaped linear bank (mlp_rollout_kernel): T steps of actor + Gaussian sample + env step.

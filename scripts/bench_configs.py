@@ -4,6 +4,7 @@
     python scripts/bench_configs.py [--configs pong_a2c,breakout_ppo,mujoco_ppo_dp8,cartpole_cpu] [--updates K]
                                     [--warmup W] [--engine auto|torch] [--device cuda:0] [--engine-opts JSON]
                                     [--bootstrap-on-timeout] [--norm-obs] [--norm-reward]
+                                    [--target-kl X]
 
 Each config runs with its preset (config.py PRESETS): same model, env bank, rollout length, optimiser and PPO
 epochs/minibatches as BASELINE.json names; synthetic envs and random-init weights. The update is captured as a
@@ -25,7 +26,7 @@ import torch  # noqa: E402
 
 
 def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None, bootstrap_on_timeout=False,
-        norm_obs=False, norm_reward=False):
+        norm_obs=False, norm_reward=False, target_kl=None):
     from actor_critic_algs_on_tensorflow_amd import preset
     from actor_critic_algs_on_tensorflow_amd.algos.trainer import ActorCriticTrainer
     dev = device if name != "cartpole_cpu" or device == "cpu" else device
@@ -37,6 +38,8 @@ def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None
         cfg = cfg.replace(norm_obs=True)   # (validated: MLP configs only)
     if norm_reward:
         cfg = cfg.replace(norm_reward=True)   # (validated: MLP configs only)
+    if target_kl is not None:
+        cfg = cfg.replace(target_kl=target_kl)   # (validated: PPO configs only; a CNN config runs on the torch engine)
     if engine_opts:
         import dataclasses
         cfg.engine_opts = dataclasses.replace(cfg.engine_opts, **engine_opts)
@@ -67,7 +70,10 @@ def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None
         torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     steps = cfg.n_steps * tr.env.num_envs * updates
-    return {"config": name, "env_steps_per_s": round(steps / dt, 1), "ms_per_update": round(1e3 * dt / updates, 4),
+    # early stopping: the optimiser steps the last update applied and the approximate KL that ended (or closed) it
+    kl = {"target_kl": cfg.target_kl, "ppo_steps": int(tr.stats["ppo_steps"]),
+          "approx_kl": float(tr.stats["approx_kl"])} if cfg.target_kl is not None else {"target_kl": None}
+    return {**kl, "config": name, "env_steps_per_s": round(steps / dt, 1), "ms_per_update": round(1e3 * dt / updates, 4),
             "updates": updates, "envs": tr.env.num_envs, "n_steps": cfg.n_steps, "algo": cfg.algo,
             "engine": "native-cnn" if tr.engine is not None else ("native-mlp" if tr.mlp is not None else "torch"),
             "hipgraph": bool(tr.graph), "device": dev, "dp_world1": bool(dp_world1),
@@ -95,11 +101,13 @@ def main():
                     help="set TrainConfig.norm_obs on the chosen configs (MLP models)")
     ap.add_argument("--norm-reward", action="store_true",
                     help="set TrainConfig.norm_reward on the chosen configs (MLP models)")
+    ap.add_argument("--target-kl", type=float, default=None,
+                    help="set TrainConfig.target_kl on the chosen configs (PPO; early stopping on the approximate KL)")
     args = ap.parse_args()
     opts = json.loads(args.engine_opts) if args.engine_opts else None
     for name in args.configs.split(","):
         res = run(name, args.updates, args.warmup, args.engine, args.device, args.dp_world1, opts,
-                  args.bootstrap_on_timeout, args.norm_obs, args.norm_reward)
+                  args.bootstrap_on_timeout, args.norm_obs, args.norm_reward, args.target_kl)
         os.write(out_fd, (json.dumps(res) + "\n").encode())
 
 
