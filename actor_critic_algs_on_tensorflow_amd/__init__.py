@@ -13,11 +13,11 @@ from .config import PRESETS, TrainConfig, preset
 
 __version__ = "0.1.0"
 
-__all__ = ["TrainConfig", "preset", "PRESETS", "train", "Agent", "_native"]
+__all__ = ["TrainConfig", "preset", "PRESETS", "train", "Agent", "evaluate_policy", "_native"]
 
 
 def __getattr__(name):
-    if name in ("train", "Agent", "TrainResult"):
+    if name in ("train", "Agent", "TrainResult", "evaluate_policy"):
         from . import api
         return getattr(api, name)
     raise AttributeError(name)

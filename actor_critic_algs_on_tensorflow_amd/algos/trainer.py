@@ -144,6 +144,8 @@ class ActorCriticTrainer:
             self._check_norm_reward()
         if cfg.target_kl is not None:
             self._check_target_kl()
+        if cfg.eval_every:
+            self._check_eval()
         if dp is not None:
             dp.broadcast_params(self.flat)
             if cfg.grad_bucket_dtype == "bf16" and dp.compress is None:
@@ -247,6 +249,20 @@ class ActorCriticTrainer:
                                  torch.tensor(float(cfg.target_kl), dtype=torch.float32))
             for opt in self.opts.values():
                 opt.set_gate(self._kl_state[0:1])
+        # periodic deterministic evaluation (algos/evaluator.py): a second bank with the training bank's env id, frame
+        # stack and time limit, sharing the MLP engine and the observation normaliser (read only). Built here, outside
+        # any capture; its graph, when captured, is its own and never part of the update's.
+        self.evaluator = None
+        self.eval_history = []
+        if cfg.eval_every:
+            from .evaluator import Evaluator
+            eseed = cfg.eval_seed if cfg.eval_seed is not None else (cfg.seed * 2654435761 + 0x9E3779B9) & 0x7FFFFFFF
+            if cfg.eval_seed is None and eseed == (cfg.seed & 0xFFFFFFFF):
+                eseed ^= 1
+            ebank = E.make(cfg.env, cfg.eval_envs, device=self.device, seed=eseed, frame_stack=self.env.frame_stack,
+                           max_episode_steps=self.env.max_episode_steps)
+            self.evaluator = Evaluator(self.model, ebank, self.mlp, self.obs_norm, cfg.eval_episodes,
+                                       cuda_graph=cfg.cuda_graph, fused=cfg.fused_rollout)
         self.iteration = 0
         self.env_steps = 0
         self.graph = None
@@ -311,6 +327,47 @@ class ActorCriticTrainer:
         if self.cfg.engine == "native" and isinstance(self.model, CNNActorCritic):
             raise ValueError("target_kl with engine='native' and a CNN model: the native CNN engine has no early-stop "
                              "gate; use engine='auto' (falls back to the torch engine) or 'torch'")
+
+    def _check_eval(self):
+        """``eval_every`` covers the MLP models under a2c / ppo on one rank."""
+        from ..models.policy import MLPActorCritic
+        if self.cfg.algo not in ("a2c", "ppo"):
+            raise ValueError(f"eval_every with algo={self.cfg.algo!r}: the reference-parity trainers (a3c, basic_ac) "
+                             "score policies with the reference's test loop (api.evaluate); use a2c or ppo")
+        if not isinstance(self.model, MLPActorCritic):
+            raise ValueError("eval_every with a CNN model: the batched deterministic evaluator covers the MLP models; "
+                             "the native CNN engine has no evaluation mode yet")
+        if self.dp is not None:
+            raise ValueError("eval_every under data parallelism: every rank would score the same policy on its own "
+                             "copy of the evaluation bank, and sharing the bank between ranks is not built yet; run "
+                             "on one rank or leave eval_every=0")
+        if int(self.cfg.eval_envs) < 1 or int(self.cfg.eval_episodes) < 1 or int(self.cfg.eval_every) < 0:
+            raise ValueError(f"eval_every={self.cfg.eval_every}, eval_envs={self.cfg.eval_envs}, "
+                             f"eval_episodes={self.cfg.eval_episodes}: the counts must be positive")
+        if self.env.max_episode_steps is None:
+            raise ValueError("eval_every needs a bank with a time limit (max_episode_steps): the evaluation's step "
+                             "budget is eval_episodes * max_episode_steps")
+
+    def evaluate(self):
+        """One deterministic evaluation of the current parameters (and observation-normaliser tables) on the
+        evaluation bank: the summary and per-episode arrays of :meth:`Evaluator.result` (one host read)."""
+        if self.evaluator is None:
+            raise ValueError("evaluate() needs TrainConfig.eval_every > 0 (the evaluation bank is built with the "
+                             "trainer)")
+        return self.evaluator.evaluate()
+
+    def _eval_row(self, it):
+        r = self.evaluate()
+        row = dict(iteration=it, env_steps=self.env_steps, eval_ret_mean=r["ret_mean"], eval_ret_std=r["ret_std"],
+                   eval_ret_min=r["ret_min"], eval_ret_max=r["ret_max"], eval_len=r["len_mean"],
+                   eval_episodes=r["episodes"])
+        self.eval_history.append(row)
+        if self.logger is not None:
+            self.logger.log_metrics(**row)
+        if self.tb is not None:
+            self.tb.writer.add_scalars({"eval/" + k[5:]: float(v) for k, v in row.items() if k.startswith("eval_")},
+                                       it)
+        return row
 
     def _scale_rewards(self):
         """After the rollout wrote the raw rewards, before any bootstrap term: scan, merge (under DP one small
@@ -1506,6 +1563,8 @@ class ActorCriticTrainer:
             self._maybe_fault()
             self.step()
             it = self.iteration - 1
+            if self.evaluator is not None and it % cfg.eval_every == 0:
+                self._eval_row(it)
             if cfg.stdout_freq and it % cfg.stdout_freq == 0:
                 s = self.log(it, print_tog=not cfg.quiet)
                 if s is not None:

@@ -39,6 +39,9 @@ def build_parser():
     p.add_argument("--target-kl", default=None, type=float,
                    help="PPO early stopping: skip an update's remaining minibatch steps once the approximate KL "
                         "exceeds 1.5 x this (TrainConfig.target_kl; --algo ppo, one device)")
+    p.add_argument("--eval-every", default=0, type=int,
+                   help="deterministic evaluation on a second bank after every N-th update (TrainConfig.eval_every; "
+                        "--algo a2c|ppo, MLP models, one device)")
     return p
 
 
@@ -62,6 +65,8 @@ def main(argv=None):
         kw["norm_reward"] = True
     if a.target_kl is not None:
         kw["target_kl"] = a.target_kl
+    if a.eval_every:
+        kw["eval_every"] = a.eval_every
     cfg = preset(name, **kw)
     res = train(cfg)
     print("done: %d iterations, %d env steps, %.1f env-steps/s" % (res.iterations, res.env_steps,

@@ -131,6 +131,15 @@ class TrainConfig:
     # (the captured update issues nothing from the host). PPO on the torch engine and the native MLP engine; no data
     # parallelism yet. None = off
     target_kl: float | None = None
+    # -- evaluation ----------------------------------------------------------------------------------------------
+    # periodic deterministic evaluation (algos/evaluator.py): after every eval_every-th update the policy's mean /
+    # arg-max actions are scored on a second bank of eval_envs envs (same env id, frames and time limit; RNG seed
+    # eval_seed) that is put back to the same start states each time, eval_episodes episodes per env, raw rewards. It
+    # writes nothing the trainer reads. MLP models under a2c / ppo on one rank; 0 = off
+    eval_every: int = 0
+    eval_envs: int = 16
+    eval_episodes: int = 1
+    eval_seed: int | None = None      # None: derived from seed (and different from it)
     # -- execution -----------------------------------------------------------------------------------------------
     dtype: str = "bf16"               # compute dtype of the GPU engine (fp32 masters always)
     engine: str = "auto"              # auto | native (hand-written HIP engine) | torch (autograd reference)
@@ -208,6 +217,18 @@ class TrainConfig:
             if self.engine == "native" and self.model == "cnn":
                 raise ValueError("TrainConfig.target_kl with engine='native' and model='cnn': the native CNN engine "
                                  "has no early-stop gate; use engine='auto' or 'torch'")
+        if int(self.eval_every) < 0:
+            raise ValueError(f"TrainConfig.eval_every={self.eval_every}: must be >= 0 (updates; 0 = no evaluation)")
+        if self.eval_every:
+            if self.algo in ("a3c", "basic_ac"):
+                raise ValueError(f"TrainConfig.eval_every with algo={self.algo!r}: the reference-parity trainers score "
+                                 "policies with the reference's test loop (api.evaluate); use a2c or ppo")
+            if self.model == "cnn":
+                raise ValueError("TrainConfig.eval_every with model='cnn': the batched deterministic evaluator covers "
+                                 "the MLP models; the native CNN engine has no evaluation mode yet")
+        if int(self.eval_envs) < 1 or int(self.eval_episodes) < 1:
+            raise ValueError(f"TrainConfig.eval_envs={self.eval_envs}, eval_episodes={self.eval_episodes}: both must "
+                             "be >= 1")
         if self.look_ahead is not None and int(self.look_ahead) < 1:
             raise ValueError(f"TrainConfig.look_ahead={self.look_ahead}: must be >= 1 (None = the whole rollout)")
 

@@ -20,6 +20,10 @@ per 16 rows with its activations in LDS, on f32 MFMA:
   observation of every step the time limit cut, in :func:`timeout_slots` compact slots per env; one more critic launch
   over those ``N S`` stacks and one fix-up launch (``ops/returns.py`` ``timeout_bootstrap_``) then add
   ``gamma V(terminal observation)`` to the truncated steps' rewards (``TrainConfig.bootstrap_on_timeout``).
+* :meth:`MLPEngine.rollout_eval_linear` -- the deterministic evaluation of that bank in ONE launch (the ``EVAL``
+  instantiations of ``mlp_rollout_kernel``: the actor's mean, no noise, nothing stored per step, episode records
+  written as episodes end); ``policy_step(greedy=True)`` is the per-step form for every other bank
+  (``algos/evaluator.py``).
 
 Weights are read in place from the fp32 parameter slab (TF ``[in, out]`` kernels, so checkpoints need no
 transposes) and gradients are written straight into the gradient slab.
@@ -234,7 +238,7 @@ class MLPEngine:
     def _fwd(self, mode, obs, B, tw_base=0, ntw=2, desc_B=None, idx=None, perm=None, tg=None, env_ids=None, key_shift=0,
              seed=0, act_out=None, logp_out=None, ent_out=None, v_out=None, act_in=None, logp_old=None, adv=None,
              ret=None, v_old=None, ent_coef=None, kl_coef=None, vf_coef=1.0, ppo_clip=0.0, v_clip=0.0, ppo=False,
-             stamps=None, go=None):
+             stamps=None, go=None, greedy=False):
         ops = _native.require()
         desc, _ = self.desc(desc_B)
         obs2 = obs.reshape(obs.shape[0], -1)
@@ -246,13 +250,16 @@ class MLPEngine:
                     act_in, logp_old, adv, ret, v_old, ent_coef, kl_coef, float(vf_coef), float(ppo_clip),
                     float(v_clip or 0.0), bool(ppo), self.g_log_std if mode == 2 else None,
                     self.mstats if mode == 2 else None, self._mpart(B) if mode == 2 else None, stamps,
-                    self._hdescs[desc_B] if (mode == 2 and self.spec) else None, tables, nclip, go)
+                    self._hdescs[desc_B] if (mode == 2 and self.spec) else None, tables, nclip, go, bool(greedy))
 
     # ------------------------------------------------------------------------------------------- API
-    def policy_step(self, obs, act_out, logp_out, ent_out, v_out, tg, env_ids, key_shift, seed):
-        """Rollout step over the env bank: actions, log-probs, entropies and values in one launch."""
+    def policy_step(self, obs, act_out, logp_out, ent_out, v_out, tg, env_ids, key_shift, seed, greedy=False):
+        """Rollout step over the env bank: actions, log-probs, entropies and values in one launch. ``greedy``: the
+        deterministic action instead of a sample -- the Gaussian mean ``tanh(y) * ac_scale`` / the first index of the
+        largest logit (``model.act(deterministic=True)``); no random number is drawn (``tg``, ``env_ids``, ``seed``
+        are not read), the log-prob is that action's, entropy and value are unchanged."""
         self._fwd(0, obs, obs.shape[0], 0, 2, tg=tg, env_ids=env_ids, key_shift=key_shift, seed=seed,
-                  act_out=act_out, logp_out=logp_out, ent_out=ent_out, v_out=v_out)
+                  act_out=act_out, logp_out=logp_out, ent_out=ent_out, v_out=v_out, greedy=greedy)
 
     def value(self, obs, out):
         self._fwd(1, obs, obs.shape[0], 1, 1, v_out=out)
@@ -398,3 +405,18 @@ class MLPEngine:
             from .returns import timeout_bootstrap_
             self.value(boot.final_obs.view(N * boot.S, -1), boot.final_v.view(-1))
             timeout_bootstrap_(st.rewards, boot.final_step, boot.final_v, boot.gamma)
+
+    def rollout_eval_linear(self, env, obs0, steps, rec):
+        """Deterministic evaluation of the MuJoCo-shaped bank ``env`` in ONE launch (the ``EVAL`` instantiations of
+        ``mlp_rollout_kernel``): ``steps`` steps of actor mean + env step from the first observation stack ``obs0``
+        ``[N, D]``; nothing is stored per step, no noise is drawn, and the first ``rec.E`` finished episodes of every
+        env go to ``rec`` (an ``ops/evaluation.py`` EvalRecords). The bank's ``state``, ``t``, ``tg`` and ``ep_ret`` are
+        advanced and written back; ``ep_stats`` and ``obs0`` are not touched. With an observation normaliser attached
+        layer 0 reads the tile normalised by the tables as they stand."""
+        desc, _ = self.desc(None)
+        wlds = self.rollout_weights_in_lds()
+        tables, nclip = self.obs_norm.kernel_args() if self.obs_norm is not None else (None, 0.0)
+        _native.require().mlp_rollout_eval(desc, self.rollout_lds_bytes(wlds), obs0, int(steps), self.log_std,
+                                           self.ac_scale, env.state, env.t, env.tg, env.ep_ret, env.env_ids, env.A,
+                                           env.B, env.seed, env.max_episode_steps, env.frame_stack, wlds,
+                                           rec.ep_ret, rec.ep_len, rec.cnt, tables, nclip)

@@ -976,7 +976,7 @@ void mlp_fwd(Tensor desc, int64_t tw_base, int64_t ntw, int64_t mode, int64_t ld
              double vf_coef, double ppo_clip, double v_clip, bool ppo, c10::optional<Tensor> g_log_std,
              c10::optional<Tensor> mstats, c10::optional<Tensor> mpart, c10::optional<Tensor> stamps,
              c10::optional<Tensor> hdesc, c10::optional<Tensor> norm_tables, double norm_clip,
-             c10::optional<Tensor> go) {
+             c10::optional<Tensor> go, bool greedy) {
   need(desc, at::kLong, "desc");
   TORCH_CHECK(desc.numel() * 8 >= (int64_t)(2 * sizeof(aca::MlpTower)), "mlp_fwd: desc too small");
   TORCH_CHECK(obs.is_cuda() && obs.scalar_type() == at::kFloat && obs.dim() == 2 && obs.stride(1) == 1,
@@ -1082,6 +1082,9 @@ void mlp_fwd(Tensor desc, int64_t tw_base, int64_t ntw, int64_t mode, int64_t ld
   // PPO early-stop flag (target_kl): train launches only
   a.go = copt<int32_t>(go, at::kInt, "go");
   if (a.go) TORCH_CHECK(mode == 2 && go->numel() >= 1, "mlp_fwd: go is one int32 flag of a train launch");
+  // deterministic actions (mean / first arg-max): rollout launches only
+  TORCH_CHECK(!greedy || mode == 0, "mlp_fwd: greedy is a flag of rollout launches (mode 0)");
+  a.greedy = greedy ? 1 : 0;
   check(aca_mlp_fwd(&a, (int)ntw, (size_t)lds, spec, cur_stream(obs)), "mlp_fwd");
 }
 
@@ -1277,6 +1280,124 @@ void mlp_rollout(Tensor desc, int64_t lds, Tensor obs, Tensor act, Tensor logp, 
     a.norm_clip = (float)norm_clip;
   }
   check(aca_mlp_rollout(&a, (size_t)lds, cur_stream(obs)), "mlp_rollout");
+}
+
+// Deterministic evaluation of the MuJoCo-shaped bank in one launch (the EVAL instantiations of mlp_rollout_kernel):
+// obs0 = the bank's first observation stack [N, D] (read only); rec_ret fp32 / rec_len int32 [N, E], rec_cnt int32 [N].
+// The record tensors select the instantiation; what the launcher rejects (records missing, or records together with
+// the bootstrap's final_obs slots) is passed through to it and raises from there, before anything is launched.
+void mlp_rollout_eval(Tensor desc, int64_t lds, Tensor obs0, int64_t steps, Tensor log_std, Tensor ac_scale,
+                      Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor env_ids, Tensor lin_A, Tensor lin_B,
+                      int64_t env_seed, int64_t max_steps, int64_t k, bool wlds, c10::optional<Tensor> rec_ret,
+                      c10::optional<Tensor> rec_len, c10::optional<Tensor> rec_cnt,
+                      c10::optional<Tensor> norm_tables, double norm_clip, c10::optional<Tensor> final_obs,
+                      c10::optional<Tensor> final_step) {
+  need(desc, at::kLong, "desc");
+  TORCH_CHECK(desc.numel() * 8 >= (int64_t)sizeof(aca::MlpTower), "mlp_rollout_eval: desc too small");
+  need(obs0, at::kFloat, "obs0");
+  need(state, at::kFloat, "state");
+  need(t, at::kInt, "t");
+  need(tg, at::kLong, "tg");
+  need(ep_ret, at::kFloat, "ep_ret");
+  need(env_ids, at::kLong, "env_ids");
+  need(log_std, at::kFloat, "log_std");
+  need(ac_scale, at::kFloat, "ac_scale");
+  need(lin_A, at::kFloat, "lin_A");
+  need(lin_B, at::kFloat, "lin_B");
+  TORCH_CHECK(obs0.dim() == 2, "mlp_rollout_eval: obs0 must be [N, D]");
+  const int64_t N = obs0.size(0), D = obs0.size(1);
+  TORCH_CHECK(steps >= 1 && steps < INT32_MAX && N >= 1 && N < INT32_MAX && k >= 1 && D == 17 * k &&
+                  state.numel() == N * 17, "mlp_rollout_eval: bad steps / obs0 / state shapes");
+  TORCH_CHECK(t.numel() == N && tg.numel() == N && ep_ret.numel() == N && env_ids.numel() == N,
+              "mlp_rollout_eval: env bank buffers must be [N]");
+  TORCH_CHECK(log_std.numel() == 6 && ac_scale.numel() == 6 && lin_A.numel() == 17 * 17 && lin_B.numel() == 17 * 6,
+              "mlp_rollout_eval: bad head / dynamics shapes");
+  aca::RolloutArgs a{};
+  a.tw = reinterpret_cast<const aca::MlpTower*>(desc.data_ptr());
+  a.N = (int)N;
+  a.T = (int)steps;
+  a.D = (int)D;
+  a.A = 6;
+  a.head = 2;
+  a.k = (int)k;
+  a.log_std = ptr<float>(log_std);
+  a.ac_scale = ptr<float>(ac_scale);
+  a.obs = ptr<float>(obs0);
+  a.state = ptr<float>(state);
+  a.t = ptr<int32_t>(t);
+  a.tg = ptr<int64_t>(tg);
+  a.ep_ret = ptr<float>(ep_ret);
+  a.env_ids = ptr<int64_t>(env_ids);
+  a.lin_A = ptr<float>(lin_A);
+  a.lin_B = ptr<float>(lin_B);
+  a.env_seed = (uint32_t)env_seed;
+  a.max_steps = (int)max_steps;
+  a.wlds = wlds ? 1 : 0;
+  TORCH_CHECK(has(rec_ret) == has(rec_len) && has(rec_ret) == has(rec_cnt),
+              "mlp_rollout_eval: rec_ret, rec_len and rec_cnt go together");
+  if (has(rec_ret)) {
+    need(*rec_ret, at::kFloat, "rec_ret");
+    need(*rec_len, at::kInt, "rec_len");
+    need(*rec_cnt, at::kInt, "rec_cnt");
+    TORCH_CHECK(rec_ret->dim() == 2 && rec_ret->size(0) == N && rec_ret->size(1) >= 1 &&
+                    rec_len->sizes() == rec_ret->sizes() && rec_cnt->numel() == N,
+                "mlp_rollout_eval: rec_ret / rec_len must be [N, E], rec_cnt [N]");
+    a.ev_ret = ptr<float>(*rec_ret);
+    a.ev_len = ptr<int32_t>(*rec_len);
+    a.ev_cnt = ptr<int32_t>(*rec_cnt);
+    a.E = (int)rec_ret->size(1);
+  }
+  TORCH_CHECK(has(final_obs) == has(final_step), "mlp_rollout_eval: final_obs and final_step go together");
+  if (has(final_obs)) {
+    need(*final_obs, at::kFloat, "final_obs");
+    need(*final_step, at::kInt, "final_step");
+    TORCH_CHECK(final_obs->dim() == 3 && final_obs->size(0) == N && final_obs->size(1) >= 1 &&
+                    final_obs->size(2) == D && final_step->numel() == N * final_obs->size(1),
+                "mlp_rollout_eval: final_obs must be [N, S, D], final_step [N, S]");
+    a.final_obs = ptr<float>(*final_obs);
+    a.final_step = ptr<int32_t>(*final_step);
+    a.S = (int)final_obs->size(1);
+  }
+  if (has(norm_tables)) {
+    need(*norm_tables, at::kFloat, "norm_tables");
+    TORCH_CHECK(norm_tables->numel() == 2 * D && norm_clip > 0, "mlp_rollout_eval: norm_tables must be [2, D] with a "
+                "positive clip");
+    a.norm_mean = ptr<float>(*norm_tables);
+    a.norm_istd = a.norm_mean + D;
+    a.norm_clip = (float)norm_clip;
+  }
+  check(aca_mlp_rollout(&a, (size_t)lds, cur_stream(obs0)), "mlp_rollout_eval");
+}
+
+// ---------------------------------------------------------------------------------------------- evaluation records
+// rewards fp32 / dones uint8 [L, N] contiguous -> rec_ret fp32 / rec_len int32 [N, E], rec_cnt int32 [N]
+// (eval_scan_args.h; oracle: ops/evaluation.py eval_scan_ref)
+int64_t eval_scan_unroll() { return aca_eval_scan_unroll(); }
+
+void eval_scan(Tensor rewards, Tensor dones, Tensor rec_ret, Tensor rec_len, Tensor rec_cnt) {
+  need(rewards, at::kFloat, "rewards");
+  need(dones, at::kByte, "dones");
+  need(rec_ret, at::kFloat, "rec_ret");
+  need(rec_len, at::kInt, "rec_len");
+  need(rec_cnt, at::kInt, "rec_cnt");
+  TORCH_CHECK(rewards.dim() == 2 && dones.sizes() == rewards.sizes(), "eval_scan: rewards and dones must be [L, N]");
+  const int64_t L = rewards.size(0), N = rewards.size(1);
+  TORCH_CHECK(L >= 1 && N >= 1 && L < INT32_MAX && N < INT32_MAX, "eval_scan: L >= 1, N >= 1");
+  TORCH_CHECK(rec_ret.dim() == 2 && rec_ret.size(0) == N && rec_ret.size(1) >= 1 && rec_ret.size(1) < INT32_MAX &&
+                  rec_len.sizes() == rec_ret.sizes() && rec_cnt.numel() == N,
+              "eval_scan: rec_ret / rec_len must be [N, E], rec_cnt [N] for rewards [L, N]");
+  for (const Tensor* x : {&dones, &rec_ret, &rec_len, &rec_cnt})
+    TORCH_CHECK(x->device() == rewards.device(), "eval_scan: every operand on one GPU");
+  aca::EvalScanArgs a{};
+  a.reward = ptr<float>(rewards);
+  a.done = ptr<uint8_t>(dones);
+  a.ep_ret = ptr<float>(rec_ret);
+  a.ep_len = ptr<int32_t>(rec_len);
+  a.cnt = ptr<int32_t>(rec_cnt);
+  a.L = (int)L;
+  a.N = (int)N;
+  a.E = (int)rec_ret.size(1);
+  check(aca_eval_scan(&a, cur_stream(rewards)), "eval_scan");
 }
 
 // ---------------------------------------------------------------------------------------------- observation normaliser
@@ -2211,7 +2332,7 @@ TORCH_LIBRARY(acamd, m) {
         "Tensor? act_out, Tensor? logp_out, Tensor? ent_out, Tensor? v_out, Tensor? act_in, Tensor? logp_old, "
         "Tensor? adv, Tensor? ret, Tensor? v_old, Tensor? ent_coef, Tensor? kl_coef, float vf_coef, float ppo_clip, "
         "float v_clip, bool ppo, Tensor? g_log_std, Tensor? mstats, Tensor? mpart=None, Tensor? stamps=None, Tensor? hdesc=None, "
-        "Tensor? norm_tables=None, float norm_clip=0.0, Tensor? go=None) -> ()");
+        "Tensor? norm_tables=None, float norm_clip=0.0, Tensor? go=None, bool greedy=False) -> ()");
   m.def("mlp_wgrad(Tensor items, int nrt, int nsplit, Tensor? g_log_std, int A, Tensor? ls_part, float ls_clip, "
         "Tensor? stats, Tensor ent_coef, Tensor kl_coef, Tensor mpart, int mpart_rows, Tensor? bump, "
         "Tensor? kl_stat=None, Tensor? go=None, float kl_thr=0.0, Tensor? kl_trace=None, int kl_step=0) -> ()");
@@ -2223,6 +2344,12 @@ TORCH_LIBRARY(acamd, m) {
         "Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, Tensor lin_A, "
         "Tensor lin_B, int env_seed, int max_steps, int k, bool wlds, Tensor? stamps=None, Tensor? final_obs=None, "
         "Tensor? final_step=None, Tensor? norm_tables=None, float norm_clip=0.0) -> ()");
+  m.def("mlp_rollout_eval(Tensor desc, int lds, Tensor obs0, int steps, Tensor log_std, Tensor ac_scale, "
+        "Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor env_ids, Tensor lin_A, Tensor lin_B, int env_seed, "
+        "int max_steps, int k, bool wlds, Tensor? rec_ret, Tensor? rec_len, Tensor? rec_cnt, "
+        "Tensor? norm_tables=None, float norm_clip=0.0, Tensor? final_obs=None, Tensor? final_step=None) -> ()");
+  m.def("eval_scan_unroll() -> int", &eval_scan_unroll);
+  m.def("eval_scan(Tensor rewards, Tensor dones, Tensor rec_ret, Tensor rec_len, Tensor rec_cnt) -> ()");
   m.def("obs_norm_parts(int R) -> int", &obs_norm_parts);
   m.def("obs_norm_prepare(Tensor obs, Tensor plane, Tensor tables, Tensor state, Tensor part, int r_stat, "
         "float clip) -> ()");
@@ -2317,6 +2444,8 @@ TORCH_LIBRARY_IMPL(acamd, CUDA, m) {
   m.impl("mlp_tshadow", &mlp_tshadow);
   m.impl("mlp_wgrad", &mlp_wgrad);
   m.impl("mlp_rollout", &mlp_rollout);
+  m.impl("mlp_rollout_eval", &mlp_rollout_eval);
+  m.impl("eval_scan", &eval_scan);
   m.impl("timeout_bootstrap", &timeout_bootstrap);
   m.impl("obs_norm_prepare", &obs_norm_prepare);
   m.impl("obs_norm_merge", &obs_norm_merge);

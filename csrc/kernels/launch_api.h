@@ -15,6 +15,7 @@
 
 #include "cnn_args.h"
 #include "env_args.h"
+#include "eval_scan_args.h"
 #include "gemm_desc.h"
 #include "loss_args.h"
 #include "mlp_desc.h"
@@ -126,6 +127,10 @@ hipError_t aca_obs_norm_merge(const aca::ObsNormMergeArgs* a, hipStream_t stream
 int aca_reward_norm_unroll(void);   // RWN_UNROLL: time steps per load round of the scan
 hipError_t aca_reward_norm_scan(const aca::RewardNormScanArgs* a, hipStream_t stream);
 hipError_t aca_reward_norm_apply(const aca::RewardNormApplyArgs* a, hipStream_t stream);
+
+// ---- evaluation records from stored reward / done columns (eval_scan.hip)
+int aca_eval_scan_unroll(void);   // EVS_UNROLL: time steps per load round of the scan
+hipError_t aca_eval_scan(const aca::EvalScanArgs* a, hipStream_t stream);
 
 // ---- GEMM and explicit conv plumbing (gemm*.hip, conv.hip)
 int aca_gemm_tile_dims(int tile, int* bm, int* bn);

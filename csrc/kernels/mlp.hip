@@ -547,8 +547,10 @@ __device__ __forceinline__ float kl_term(float x, float r) {
 }
 
 // one tower of mlp_fwd_kernel. SPEC 0: any tower (t at run time, layer loops over the device descriptor); SPEC > 0:
-// tower TW of the reference shapes in train mode, weights from registers.
-template <int SPEC, int TW>
+// tower TW of the reference shapes in train mode, weights from registers. GREEDY (generic path, rollout launches with
+// MlpArgs::greedy): the heads return their deterministic action; an instantiation of its own, so that every other
+// launch runs the code it ran without the flag.
+template <int SPEC, int TW, bool GREEDY = false>
 __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* sm, MlpShared& S) {
   constexpr bool SP = SPEC > 0;
   using Regs = typename std::conditional<TW == 0, ActorRegs<SP ? SPEC : 1>, CriticRegs<SP ? SPEC : 1>>::type;
@@ -970,10 +972,14 @@ __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* 
         const float mu = th * S.hsc[j];
         float aj;
         if (a.mode == 0) {
-          const int64_t key = live ? row_key(a, (int)grow) : 0;
-          const float u1 = uniform_open(a.seed, key, 2 * j), u2 = uniform_open(a.seed, key, 2 * j + 1);
-          const float eps = sqrtf(-2.0f * logf(u1)) * cosf(TWO_PI * u2);
-          aj = mu + expf(ls) * eps;
+          if constexpr (GREEDY) {   // the mean: zz below is exactly 0, no key is hashed
+            aj = mu;
+          } else {
+            const int64_t key = live ? row_key(a, (int)grow) : 0;
+            const float u1 = uniform_open(a.seed, key, 2 * j), u2 = uniform_open(a.seed, key, 2 * j + 1);
+            const float eps = sqrtf(-2.0f * logf(u1)) * cosf(TWO_PI * u2);
+            aj = mu + expf(ls) * eps;
+          }
           if (live) a.act_f_out[grow * a.A + j] = aj;
         } else {
           aj = live ? (a.mode == 2 ? e_act : a.act_f_in[grow * a.A + j]) : mu;
@@ -1058,12 +1064,17 @@ __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* 
       for (int j = 0; j < A; ++j) { const float lpj = z[j] - lse; H -= expf(lpj) * lpj; }
       int ai = 0;
       if (a.mode == 0) {
-        const int64_t key = live ? row_key(a, (int)grow) : 0;
         float best = -INFINITY;
-        for (int j = 0; j < A; ++j) {
-          const float u = uniform_open(a.seed, key, (uint32_t)j);
-          const float gj = z[j] + (-logf(-logf(u)));
-          if (gj > best) { best = gj; ai = j; }
+        if constexpr (GREEDY) {   // first index of the largest logit (torch.argmax's tie rule), no key is hashed
+          for (int j = 0; j < A; ++j)
+            if (z[j] > best) { best = z[j]; ai = j; }
+        } else {
+          const int64_t key = live ? row_key(a, (int)grow) : 0;
+          for (int j = 0; j < A; ++j) {
+            const float u = uniform_open(a.seed, key, (uint32_t)j);
+            const float gj = z[j] + (-logf(-logf(u)));
+            if (gj > best) { best = gj; ai = j; }
+          }
         }
         if (live) a.act_i_out[grow] = ai;
       } else {
@@ -1220,7 +1231,7 @@ __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* 
   cstamp(13);
 }
 
-template <int SPEC>
+template <int SPEC, bool GREEDY = false>
 __global__ void __launch_bounds__(MLP_THREADS) mlp_fwd_kernel(MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // 16-byte base: the b128 LDS reads stay aligned
   __shared__ MlpShared S;
@@ -1229,7 +1240,7 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_fwd_kernel(MlpArgs a) {
   if (a.go && *a.go == 0) return;
   const int t = blockIdx.y + a.tw_base;
   if constexpr (SPEC == 0) {
-    mlp_tower<0, -1>(a, t, sm, S);
+    mlp_tower<0, -1, GREEDY>(a, t, sm, S);
   } else {
     if (t == 0) mlp_tower<SPEC, 0>(a, 0, sm, S);
     else mlp_tower<SPEC, 1>(a, 1, sm, S);
@@ -1600,13 +1611,18 @@ __device__ __forceinline__ void roll_layer_epilogue(const float* __restrict__ re
 // statistics -- and layer 0 reads one small normalised tile instead: filled from the step-0 tile at entry, refilled by
 // the thread that writes Xn, right after that write (the step's barriers already separate layer 0's reads from the
 // refill, so one buffer suffices). Tables and tile are static LDS of this instantiation only.
-template <int KP0, bool BOOT, bool NORM>
+// EVAL: deterministic evaluation (never with BOOT). The action is the Gaussian mean: no noise is drawn, no log-prob or
+// entropy is formed and nothing is stored per step, so the step loop issues no global load and a global store only
+// when an env finishes an episode -- the owner lane then writes the episode's return and length (s_er / s_t, the
+// bank's own accumulators) into the env's next record slot (s_ne counts them). a.obs is the first observation stack
+// [N][D] only. The bank write-back is the same and also writes the counts.
+template <int KP0, bool BOOT, bool NORM, bool EVAL = false>
 __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // 16-byte base: the b128 LDS reads stay aligned
   __shared__ int64_t s_tg[ROLL_RB];
   __shared__ int64_t s_ids[ROLL_RB];
   __shared__ int s_t[ROLL_RB];
-  __shared__ int s_ne[ROLL_RB];   // BOOT: terminal-observation slots the env has used so far
+  __shared__ int s_ne[ROLL_RB];   // BOOT: terminal-observation slots the env has used so far; EVAL: episodes recorded
   __shared__ float s_er[ROLL_RB];
   __shared__ float s_ls[MLP_MAXA], s_sc[MLP_MAXA];
   __shared__ float s_hl[ROLL_RB * MLP_MAXA];
@@ -1646,7 +1662,7 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
     s_ids[tid] = live ? a.env_ids[row0 + tid] : 0;
     s_t[tid] = live ? a.t[row0 + tid] : 0;
     s_er[tid] = live ? a.ep_ret[row0 + tid] : 0.f;
-    if constexpr (BOOT) s_ne[tid] = 0;
+    if constexpr (BOOT || EVAL) s_ne[tid] = 0;
   }
   if constexpr (NORM) {
     if (tid < KP0) {
@@ -1747,7 +1763,7 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
       if (nz_live) nkey += (int64_t)1 << a.key_shift;
     }
   };
-  noise_ahead();
+  if constexpr (!EVAL) noise_ahead();
   __syncthreads();
   // diagnostics only (stamps[255] == 1): the step loop runs the actor layers alone (no head, no env step)
   const bool layers_only = a.stamps && a.stamps[255] == 1;
@@ -1792,32 +1808,38 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
     if (tid < ROLL_RB * MLP_MAXA) {
       const int r = tid / MLP_MAXA, j = tid % MLP_MAXA;
       if (j < A) {
-        const bool live = r < rows;
+        [[maybe_unused]] const bool live = r < rows;
         const float* Yo = X + r * ldx;
-        const float ls = s_ls[j];
+        [[maybe_unused]] const float ls = s_ls[j];
         const float mu = tanhf(Yo[j]) * s_sc[j];
-        const float eps = s_epa[r * MLP_MAXA + j] * s_epb[r * MLP_MAXA + j];   // (noise_ahead: the previous step)
-        const float aj = mu + s_els[j] * eps;
-        const float zz = (aj - mu) * s_eils[j];
-        s_hl[r * MLP_MAXA + j] = -0.5f * zz * zz - ls - HALF_LOG_2PI;
-        s_act[r * MLP_MAXA + j] = aj;
-        if (live) a.act[((size_t)step * a.N + row0 + r) * A + j] = aj;
+        if constexpr (EVAL) {
+          s_act[r * MLP_MAXA + j] = mu;
+        } else {
+          const float eps = s_epa[r * MLP_MAXA + j] * s_epb[r * MLP_MAXA + j];   // (noise_ahead: the previous step)
+          const float aj = mu + s_els[j] * eps;
+          const float zz = (aj - mu) * s_eils[j];
+          s_hl[r * MLP_MAXA + j] = -0.5f * zz * zz - ls - HALF_LOG_2PI;
+          s_act[r * MLP_MAXA + j] = aj;
+          if (live) a.act[((size_t)step * a.N + row0 + r) * A + j] = aj;
+        }
       }
     }
     __syncthreads();
     stamp(step, 5);
     // (the per-env log-prob / entropy sums run on wave 3, beside the env step of waves 0-1 and wave 2's noise)
-    if (tid >= 192 && tid < 192 + rows) {
-      const int r = tid - 192;
-      float lp = 0.f, H = 0.f;
-      for (int j = 0; j < A; ++j) {
-        lp += s_hl[r * MLP_MAXA + j];
-        H += 0.5f + HALF_LOG_2PI + s_ls[j];
+    if constexpr (!EVAL) {
+      if (tid >= 192 && tid < 192 + rows) {
+        const int r = tid - 192;
+        float lp = 0.f, H = 0.f;
+        for (int j = 0; j < A; ++j) {
+          lp += s_hl[r * MLP_MAXA + j];
+          H += 0.5f + HALF_LOG_2PI + s_ls[j];
+        }
+        a.logp[(size_t)step * a.N + row0 + r] = lp;
+        a.ent[(size_t)step * a.N + row0 + r] = H;
       }
-      a.logp[(size_t)step * a.N + row0 + r] = lp;
-      a.ent[(size_t)step * a.N + row0 + r] = H;
+      noise_ahead();   // waves 2 and 4: step + 1's policy noise, beside the env step below
     }
-    noise_ahead();   // waves 2 and 4: step + 1's policy noise, beside the env step below
     // ---- env step: 32 lanes per env, lane r < 17 owns state row r (linear_step_kernel)
     {
       const int e = tid / LIN_LANES, r = tid % LIN_LANES;
@@ -1875,28 +1897,39 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
           const int k = a.k;
           const float* pv = Xc + e * ld0;
           float* xo = Xn + e * ld0;
-          float* go = a.obs + ((size_t)(step + 1) * a.N + i) * D;
+          [[maybe_unused]] float* go = a.obs + ((size_t)(step + 1) * a.N + i) * D;
           for (int f = 0; f < k - 1; ++f) {
             const float v = done ? y : pv[(f + 1) * LIN_OBS + r];
             xo[f * LIN_OBS + r] = v;
-            go[f * LIN_OBS + r] = v;
+            if constexpr (!EVAL) go[f * LIN_OBS + r] = v;
             if constexpr (NORM) s_xq[e * ld0 + f * LIN_OBS + r] = normed(v, f * LIN_OBS + r);
           }
           xo[(k - 1) * LIN_OBS + r] = y;
-          go[(k - 1) * LIN_OBS + r] = y;
+          if constexpr (!EVAL) go[(k - 1) * LIN_OBS + r] = y;
           if constexpr (NORM) s_xq[e * ld0 + (k - 1) * LIN_OBS + r] = normed(y, (k - 1) * LIN_OBS + r);
         }
         if (owner) {
-          const size_t o = (size_t)step * a.N + i;
+          [[maybe_unused]] const size_t o = (size_t)step * a.N + i;
           s_tg[e] = tg;
-          a.reward[o] = rew;
-          a.done[o] = done;
-          a.trunc[o] = trunc;
+          if constexpr (EVAL) {
+            if (done) {   // once per max_steps steps: the episode's record, plain stores from the owner lane
+              const int ne = s_ne[e];
+              if (ne < a.E) {
+                a.ev_ret[(size_t)i * a.E + ne] = er;
+                a.ev_len[(size_t)i * a.E + ne] = t;
+                s_ne[e] = ne + 1;
+              }
+            }
+          } else {
+            a.reward[o] = rew;
+            a.done[o] = done;
+            a.trunc[o] = trunc;
+          }
           s_t[e] = done ? 0 : t;
           s_er[e] = done ? 0.f : er;
         }
       }
-      add_ep_stats(a.ep_stats, owner, done, ret, len);
+      if constexpr (!EVAL) add_ep_stats(a.ep_stats, owner, done, ret, len);
     }
     __syncthreads();
     stamp(step, 6);
@@ -1907,6 +1940,7 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
     a.tg[row0 + tid] = s_tg[tid];
     a.t[row0 + tid] = s_t[tid];
     a.ep_ret[row0 + tid] = s_er[tid];
+    if constexpr (EVAL) a.ev_cnt[row0 + tid] = s_ne[tid];
     if constexpr (BOOT)   // unused slots: the table is valid after every launch without a host-side clear
       for (int s = s_ne[tid]; s < a.S; ++s) a.final_step[(size_t)(row0 + tid) * a.S + s] = -1;
   }
@@ -1928,6 +1962,20 @@ extern "C" hipError_t aca_mlp_fwd(const MlpArgs* a, int ntw, size_t lds, int spe
   if ((a->norm_mean != nullptr) != (a->norm_istd != nullptr) || (a->norm_mean && a->mode == 2))
     return hipErrorInvalidValue;
   if (a->go && a->mode != 2) return hipErrorInvalidValue;   // the early-stop flag gates train launches only
+  // deterministic actions: rollout launches of the generic kernel only, in an instantiation of their own
+  if (a->greedy && (a->mode != 0 || spec != 0)) return hipErrorInvalidValue;
+  if (a->greedy) {
+    static bool gattr = false;
+    if (!gattr) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fwd_kernel<0, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) != hipSuccess)
+        return hipErrorInvalidValue;
+      gattr = true;
+    }
+    if (lds > 140 * 1024) return hipErrorInvalidValue;
+    mlp_fwd_kernel<0, true><<<dim3((a->B + MLP_BM - 1) / MLP_BM, ntw), MLP_THREADS, lds, stream>>>(*a);
+    return hipGetLastError();
+  }
   static bool attr = false;
   if (!attr) {
     const void* ks[4] = {reinterpret_cast<const void*>(&mlp_fwd_kernel<0>),
@@ -1991,6 +2039,38 @@ extern "C" hipError_t aca_mlp_rollout(const RolloutArgs* a, size_t lds, hipStrea
   // observation normalisation: both tables or none
   const bool norm = a->norm_mean != nullptr;
   if (norm != (a->norm_istd != nullptr)) return hipErrorInvalidValue;
+  // deterministic evaluation (the record pointer selects it): records instead of storage, never with the bootstrap's
+  // slots; every other launch needs all of its storage
+  const bool eval = a->ev_ret != nullptr;
+  if (eval && (boot || !a->ev_len || !a->ev_cnt || a->E < 1 || !a->obs)) return hipErrorInvalidValue;
+  if (!eval && (!a->obs || !a->act || !a->logp || !a->ent || !a->reward || !a->done || !a->trunc))
+    return hipErrorInvalidValue;
+  if (!a->state || !a->t || !a->tg || !a->ep_ret || !a->env_ids || !a->lin_A || !a->lin_B || !a->log_std ||
+      !a->ac_scale || (!eval && !a->ep_stats))
+    return hipErrorInvalidValue;
+  const dim3 grid((a->N + ROLL_RB - 1) / ROLL_RB);
+  if (eval) {
+    static bool eattr = false;
+    if (!eattr) {
+      const void* ks[4] = {reinterpret_cast<const void*>(&mlp_rollout_kernel<32, false, false, true>),
+                           reinterpret_cast<const void*>(&mlp_rollout_kernel<64, false, false, true>),
+                           reinterpret_cast<const void*>(&mlp_rollout_kernel<32, false, true, true>),
+                           reinterpret_cast<const void*>(&mlp_rollout_kernel<64, false, true, true>)};
+      for (int i = 0; i < 4; ++i)
+        if (hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize,
+                                ROLLOUT_MAX_LDS - (i >= 2 ? ROLLOUT_NORM_LDS : 0)) != hipSuccess)
+          return hipErrorInvalidValue;
+      eattr = true;
+    }
+    if (lds > ROLLOUT_MAX_LDS - (norm ? ROLLOUT_NORM_LDS : 0)) return hipErrorInvalidValue;
+    switch ((norm ? 2 : 0) | (a->k == 1 ? 0 : 1)) {
+      case 0: mlp_rollout_kernel<32, false, false, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+      case 1: mlp_rollout_kernel<64, false, false, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+      case 2: mlp_rollout_kernel<32, false, true, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+      default: mlp_rollout_kernel<64, false, true, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    }
+    return hipGetLastError();
+  }
   static bool attr = false;
   if (!attr) {
     const void* ks[8] = {reinterpret_cast<const void*>(&mlp_rollout_kernel<32, false, false>),
@@ -2008,7 +2088,6 @@ extern "C" hipError_t aca_mlp_rollout(const RolloutArgs* a, size_t lds, hipStrea
     attr = true;
   }
   if (lds > ROLLOUT_MAX_LDS - (norm ? ROLLOUT_NORM_LDS : 0)) return hipErrorInvalidValue;
-  const dim3 grid((a->N + ROLL_RB - 1) / ROLL_RB);
   const int which = (norm ? 4 : 0) | (boot ? 2 : 0) | (a->k == 1 ? 0 : 1);
   switch (which) {
     case 0: mlp_rollout_kernel<32, false, false><<<grid, MLP_THREADS, lds, stream>>>(*a); break;

@@ -63,6 +63,10 @@ struct MlpArgs {
   // optional PPO early-stop flag (target_kl): while *go == 0 the launch returns at entry, before any store or barrier
   // (uniform over the launch; the bookkeeping workgroup of an EARLIER weight-gradient launch stored it: stream order)
   const int32_t* go;
+  // deterministic actions (mode 0 only): the Gaussian head returns its mean tanh(y) * ac_scale (the log-prob is then
+  // the fixed-order sum of -log_std - HALF_LOG_2PI), the categorical head the first index of the largest logit
+  // (torch.argmax's tie rule); no key is hashed. Entropy and value are those of the sampling launch.
+  int greedy;
 };
 
 struct WgradArgs {
@@ -127,6 +131,14 @@ struct RolloutArgs {
   // observation tile; a.obs, the frame-stack shift and final_obs stay raw. Null = off.
   const float* norm_mean; const float* norm_istd;   // [D] each
   float norm_clip;
+  // optional (deterministic evaluation, the EVAL instantiations; selected when ev_ret is set): the action is the
+  // Gaussian mean, no noise is drawn and nothing is stored per step -- obs is the bank's first observation stack
+  // [N][D], read only, and act .. trunc, ep_stats are not touched. The first E finished episodes of env i go to
+  // ev_ret[i][0 .. E) (fp32 sum of the rewards in step order, the bank's ep_ret arithmetic) and ev_len[i][0 .. E);
+  // ev_cnt[i] = how many were recorded (written by every launch; unused slots are left as they are).
+  float* ev_ret; int32_t* ev_len;   // [N][E]
+  int32_t* ev_cnt;                  // [N]
+  int E;
 };
 
 }  // namespace aca

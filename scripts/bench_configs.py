@@ -82,6 +82,42 @@ def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None
             "ppo": {"epochs": cfg.ppo_epochs, "minibatches": cfg.ppo_minibatches} if cfg.algo == "ppo" else None}
 
 
+def run_eval(name, reps, device, norm_obs=False, eval_envs=16, eval_episodes=1):
+    """The deterministic evaluation of a config (``TrainConfig.eval_every``; algos/evaluator.py) on its own: time per
+    evaluation as its captured graph replays (restore, launches, summary), and, as the yardstick of the fused path, the
+    training rollout (``collect``: rollout launch + critic launch) timed eagerly on the same trainer."""
+    from actor_critic_algs_on_tensorflow_amd import preset
+    from actor_critic_algs_on_tensorflow_amd.algos.trainer import ActorCriticTrainer
+    cuda = device.startswith("cuda")
+    cfg = preset(name, device=device, outdir=None, quiet=True, stdout_freq=0, save_every=0, cuda_graph=cuda,
+                 eval_every=1, eval_envs=eval_envs, eval_episodes=eval_episodes, norm_obs=norm_obs)
+    tr = ActorCriticTrainer(cfg)
+    ev = tr.evaluator
+
+    def timed(fn, n):
+        if cuda:
+            torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(n):
+            fn()
+        if cuda:
+            torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / n
+
+    if norm_obs:
+        tr.step()   # the tables leave the identity
+    ev.run()        # warm-up (+ capture on a GPU)
+    res = ev.result()
+    dt = timed(ev.run, reps)
+    tr.collect()
+    dt_roll = timed(tr.collect, max(1, reps // 2))
+    return {"config": name, "eval": True, "path": ev.path, "hipgraph": ev.graph is not None, "device": device,
+            "norm_obs": bool(norm_obs), "eval_envs": ev.N, "eval_steps": ev.L, "ms_per_eval": round(1e3 * dt, 4),
+            "us_per_eval_step": round(1e6 * dt / ev.L, 3), "ret_mean": res["ret_mean"], "episodes": res["episodes"],
+            "train_rollout_envs": tr.env.num_envs, "train_rollout_steps": cfg.n_steps,
+            "train_collect_ms": round(1e3 * dt_roll, 4), "train_collect_us_per_step": round(1e6 * dt_roll / cfg.n_steps, 3)}
+
+
 def main():
     # one JSON line per config on stdout: native libraries (RCCL's banner / warnings) write to fd 1 -> stderr
     sys.stdout.flush()
@@ -103,8 +139,16 @@ def main():
                     help="set TrainConfig.norm_reward on the chosen configs (MLP models)")
     ap.add_argument("--target-kl", type=float, default=None,
                     help="set TrainConfig.target_kl on the chosen configs (PPO; early stopping on the approximate KL)")
+    ap.add_argument("--eval", action="store_true",
+                    help="measure the deterministic evaluation (eval_every) of the chosen MLP configs instead of their "
+                         "updates: --updates replays of the evaluation graph (--norm-obs: with the normaliser)")
     args = ap.parse_args()
     opts = json.loads(args.engine_opts) if args.engine_opts else None
+    if args.eval:
+        for name in args.configs.split(","):
+            res = run_eval(name, args.updates, args.device, args.norm_obs)
+            os.write(out_fd, (json.dumps(res) + "\n").encode())
+        return
     for name in args.configs.split(","):
         res = run(name, args.updates, args.warmup, args.engine, args.device, args.dp_world1, opts,
                   args.bootstrap_on_timeout, args.norm_obs, args.norm_reward, args.target_kl)
