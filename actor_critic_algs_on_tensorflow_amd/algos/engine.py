@@ -334,10 +334,34 @@ class CNNEngine:
         return (self.opts.mb_index and self.implicit and self.det_wgrad and B <= self.fused_trunk_max_b
                 and B > self.trunk_rows_max_b and B >= self.large_b)
 
-    def forward(self, obs, b: _Bufs, head=True, shift_out=None, fc_parts=False, obs_idx=None):
+    def eval_bufs(self, B):
+        """Buffers of an evaluator's own for a bank of ``B`` envs: forward activations (not the per-``B`` cache of
+        :meth:`bufs`, which a trainer with as many envs reads), fc planes (not :meth:`hpart`) and a GEMM workspace."""
+        return (_Bufs(B, self.A1, self.dev, False, self.implicit),
+                torch.zeros(FC_PLANES * B * 512, dtype=torch.float32, device=self.dev), G.GemmWorkspace(self.dev))
+
+    def eval_ok(self, B):
+        """A bank of ``B`` envs can take the evaluation step (``env_policy_eval_pong``: the 8-lane arg-max, rollout
+        sized fc products)."""
+        return self.dev.type == "cuda" and 3 <= self.A1 <= 8 and 1 <= B < self.large_b
+
+    def forward_eval(self, obs, b: _Bufs, shift_out, hp, ws):
+        """Trunk + fc planes of ``obs`` for an evaluator (:meth:`forward` with ``head=False, fc_parts=True``) into the
+        buffers of :meth:`eval_bufs`; ``last_fc`` and the workspace are left as found, so nothing a trainer reads is
+        written. Returns (the trunk shifted the stack into ``shift_out``, planes written)."""
+        keep = (self.last_fc, self.ws)
+        self.ws = ws
+        try:
+            shifted = self.forward(obs, b, head=False, shift_out=shift_out, fc_parts=True, hp=hp)
+            return bool(shifted), self.last_fc[1]
+        finally:
+            self.last_fc, self.ws = keep
+
+    def forward(self, obs, b: _Bufs, head=True, shift_out=None, fc_parts=False, obs_idx=None, hp=None):
         """obs uint8 [B, 4, 84, 84] -> b.z fp32 [B, A+1] (logits | value); ``head=False`` stops at ``b.h`` (the
         rollout fuses the head into the sampling + env-step kernel). ``shift_out``: the next observation buffer,
-        whose frames 0..2 the fused trunk fills with frames 1..3 of ``obs``; returns True iff it did."""
+        whose frames 0..2 the fused trunk fills with frames 1..3 of ``obs``; returns True iff it did. ``hp``: the
+        plane buffer of the ``fc_parts`` product (default: :meth:`hpart`)."""
         B = b.B
         ws = self.ws
         b.obs = obs  # the conv1 weight gradient re-gathers its columns from the frames
@@ -385,7 +409,7 @@ class CNNEngine:
         if fc_parts and not head:
             # partial planes only: the consumer (fused policy/env kernel or fc_value) reduces, adds the bias,
             # applies ReLU and writes b.h
-            hp = self.hpart(B)
+            hp = self.hpart(B) if hp is None else hp
             S = self._fc_rollout(b, hp)
             self.last_fc = (hp, S)
             return shifted if want_shift else b.z

@@ -250,8 +250,9 @@ class ActorCriticTrainer:
             for opt in self.opts.values():
                 opt.set_gate(self._kl_state[0:1])
         # periodic deterministic evaluation (algos/evaluator.py): a second bank with the training bank's env id, frame
-        # stack and time limit, sharing the MLP engine and the observation normaliser (read only). Built here, outside
-        # any capture; its graph, when captured, is its own and never part of the update's.
+        # stack and time limit, sharing the MLP or CNN engine and the observation normaliser (read only; the CNN path
+        # brings activation and fc-plane buffers of its own). Built here, outside any capture; its graph, when
+        # captured, is its own and never part of the update's.
         self.evaluator = None
         self.eval_history = []
         if cfg.eval_every:
@@ -261,7 +262,8 @@ class ActorCriticTrainer:
                 eseed ^= 1
             ebank = E.make(cfg.env, cfg.eval_envs, device=self.device, seed=eseed, frame_stack=self.env.frame_stack,
                            max_episode_steps=self.env.max_episode_steps)
-            self.evaluator = Evaluator(self.model, ebank, self.mlp, self.obs_norm, cfg.eval_episodes,
+            self.evaluator = Evaluator(self.model, ebank, self.mlp if self.mlp is not None else self.engine,
+                                       self.obs_norm, cfg.eval_episodes,
                                        cuda_graph=cfg.cuda_graph, fused=cfg.fused_rollout)
         self.iteration = 0
         self.env_steps = 0
@@ -329,14 +331,15 @@ class ActorCriticTrainer:
                              "gate; use engine='auto' (falls back to the torch engine) or 'torch'")
 
     def _check_eval(self):
-        """``eval_every`` covers the MLP models under a2c / ppo on one rank."""
+        """``eval_every`` covers a2c / ppo on one rank: the MLP models on any device, the CNN model on a GPU."""
         from ..models.policy import MLPActorCritic
         if self.cfg.algo not in ("a2c", "ppo"):
             raise ValueError(f"eval_every with algo={self.cfg.algo!r}: the reference-parity trainers (a3c, basic_ac) "
                              "score policies with the reference's test loop (api.evaluate); use a2c or ppo")
-        if not isinstance(self.model, MLPActorCritic):
-            raise ValueError("eval_every with a CNN model: the batched deterministic evaluator covers the MLP models; "
-                             "the native CNN engine has no evaluation mode yet")
+        if not isinstance(self.model, MLPActorCritic) and self.device.type != "cuda":
+            raise ValueError("eval_every with a CNN model on a CPU device: one evaluation is eval_episodes * "
+                             "max_episode_steps conv forwards of the whole bank, minutes on a CPU; train on a GPU, or "
+                             "score a checkpoint once with api.evaluate_policy")
         if self.dp is not None:
             raise ValueError("eval_every under data parallelism: every rank would score the same policy on its own "
                              "copy of the evaluation bank, and sharing the bank between ranks is not built yet; run "

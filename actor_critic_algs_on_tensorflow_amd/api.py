@@ -216,30 +216,32 @@ class Agent:
 
 def evaluate_policy(model_path, env_id, num_envs=16, episodes=1, seed=12321, frames=1, device="cpu", engine="auto",
                     variant=None, max_episode_steps=None, cuda_graph=False):
-    """Batched deterministic evaluation of a saved MLP policy (``algos/evaluator.py`` Evaluator): the checkpoint is
-    loaded as :meth:`Agent.from_checkpoint` does (the frozen tables of a ``norm_obs`` checkpoint included), a bank of
+    """Batched deterministic evaluation of a saved MLP or CNN policy (``algos/evaluator.py`` Evaluator): the checkpoint
+    is loaded as :meth:`Agent.from_checkpoint` does (the frozen tables of a ``norm_obs`` checkpoint included), a bank of
     ``num_envs`` envs with RNG seed ``seed`` runs ``episodes`` episodes per env under the policy's mean / arg-max
     actions, and the summary (``ret_mean``, ``ret_std``, ``ret_min``, ``ret_max``, ``len_mean``, ``episodes``) comes
     back with the per-episode arrays ``ep_ret`` / ``ep_len`` ``[num_envs, episodes]``. On a GPU (``engine="auto"`` /
-    ``"native"``) the native MLP engine runs it -- the MuJoCo-shaped bank in one launch --, ``engine="torch"`` and every
-    CPU run take the PyTorch modules. Stochastic evaluation is :func:`evaluate`."""
+    ``"native"``) the native engines run it -- the MLP engine (the MuJoCo-shaped bank in one launch) or the CNN engine
+    on the Pong-shaped banks (path ``"cnn"``) --, ``engine="torch"`` and every CPU run take the PyTorch modules. The
+    image banks always stack 4 frames. Stochastic evaluation is :func:`evaluate`."""
     from .algos.evaluator import Evaluator
-    from .models.policy import MLPActorCritic
+    from .models.policy import CNNActorCritic
     if int(num_envs) < 1 or int(episodes) < 1:
         raise ValueError(f"evaluate_policy: num_envs={num_envs} and episodes={episodes} must be >= 1")
     if engine not in ("auto", "native", "torch"):
         raise ValueError(f"evaluate_policy: engine={engine!r}: expected 'auto', 'native' or 'torch'")
     agent = Agent.from_checkpoint(model_path, env_id, frames=frames, device=device, variant=variant)
-    if not isinstance(agent.model, MLPActorCritic):
-        raise ValueError("evaluate_policy covers the MLP models; the native CNN engine has no evaluation mode yet")
     agent.engine_kind = engine
+    cnn = isinstance(agent.model, CNNActorCritic)
     kw = {} if max_episode_steps is None else {"max_episode_steps": int(max_episode_steps)}
-    env = E.make(env_id, int(num_envs), device=agent.device, seed=seed, frame_stack=frames, **kw)
+    env = E.make(env_id, int(num_envs), device=agent.device, seed=seed, frame_stack=4 if cnn else frames, **kw)
     eng = agent._engine()
-    mlp = eng[1] if eng is not None and eng[0] == "mlp" else None
-    if engine == "native" and mlp is None:
-        raise ValueError("evaluate_policy: engine='native' needs an MLP model with at most 16 actions on a GPU")
-    return Evaluator(agent.model, env, mlp, agent.obs_norm, int(episodes), cuda_graph=cuda_graph).evaluate()
+    native = eng[1] if eng is not None and eng[0] == ("cnn" if cnn else "mlp") else None
+    ev = Evaluator(agent.model, env, native, agent.obs_norm, int(episodes), cuda_graph=cuda_graph)
+    if engine == "native" and ev.path == "torch":
+        raise ValueError("evaluate_policy: engine='native' needs a GPU and an MLP model with at most 16 actions, or a "
+                         "CNN model with at most 7 actions on a Pong-shaped bank")
+    return ev.evaluate()
 
 
 def evaluate(model_path, env_id, num_episodes=3, seed=12321, frames=1, animate=False, variant=None, verbose=True,

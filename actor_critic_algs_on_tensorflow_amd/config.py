@@ -135,7 +135,7 @@ class TrainConfig:
     # periodic deterministic evaluation (algos/evaluator.py): after every eval_every-th update the policy's mean /
     # arg-max actions are scored on a second bank of eval_envs envs (same env id, frames and time limit; RNG seed
     # eval_seed) that is put back to the same start states each time, eval_episodes episodes per env, raw rewards. It
-    # writes nothing the trainer reads. MLP models under a2c / ppo on one rank; 0 = off
+    # writes nothing the trainer reads. a2c / ppo on one rank: the MLP models, and the CNN model on a GPU; 0 = off
     eval_every: int = 0
     eval_envs: int = 16
     eval_episodes: int = 1
@@ -223,9 +223,10 @@ class TrainConfig:
             if self.algo in ("a3c", "basic_ac"):
                 raise ValueError(f"TrainConfig.eval_every with algo={self.algo!r}: the reference-parity trainers score "
                                  "policies with the reference's test loop (api.evaluate); use a2c or ppo")
-            if self.model == "cnn":
-                raise ValueError("TrainConfig.eval_every with model='cnn': the batched deterministic evaluator covers "
-                                 "the MLP models; the native CNN engine has no evaluation mode yet")
+            if self.model == "cnn" and str(self.device).startswith("cpu"):
+                raise ValueError("TrainConfig.eval_every with model='cnn' on a CPU device: one evaluation is "
+                                 "eval_episodes * max_episode_steps conv forwards of the whole bank, minutes on a "
+                                 "CPU; train on a GPU, or score a checkpoint once with api.evaluate_policy")
         if int(self.eval_envs) < 1 or int(self.eval_episodes) < 1:
             raise ValueError(f"TrainConfig.eval_envs={self.eval_envs}, eval_episodes={self.eval_episodes}: both must "
                              "be >= 1")

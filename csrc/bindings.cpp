@@ -305,6 +305,91 @@ void env_policy_step_pong(Tensor h, Tensor Wh, Tensor bh, Tensor z, Tensor act, 
                                  cur_stream(state)), op);
 }
 
+// Deterministic evaluation step (env_atari.hip pong_policy_eval_kernel): arg-max action from the head of h (given, or
+// reduced from the fc planes), env step, episode records [N, E]. The bank's ep_stats is not an operand. act / reward /
+// done are optional per-step columns. The launcher refuses E < 1, missing records and A + 1 outside 3..8.
+void env_policy_eval_pong(c10::optional<Tensor> h, Tensor Wh, Tensor bh, Tensor state, Tensor t, Tensor tg,
+                          Tensor ep_ret, Tensor ids, Tensor prev, Tensor out, int64_t seed, int64_t max_steps,
+                          int64_t k, bool pre_shifted, c10::optional<Tensor> hpart, int64_t planes,
+                          c10::optional<Tensor> bfc, c10::optional<Tensor> rec_ret, c10::optional<Tensor> rec_len,
+                          c10::optional<Tensor> rec_cnt, int64_t E, c10::optional<Tensor> act,
+                          c10::optional<Tensor> reward, c10::optional<Tensor> done) {
+  const char* op = "env_policy_eval_pong";
+  need(state, at::kFloat, "state");
+  need(t, at::kInt, "t");
+  need(tg, at::kLong, "tg");
+  need(ep_ret, at::kFloat, "ep_ret");
+  need(ids, at::kLong, "env_ids");
+  need(prev, at::kByte, "prev");
+  need(out, at::kByte, "out");
+  need(Wh, at::kBFloat16, "Wh");
+  need(bh, at::kFloat, "bh");
+  TORCH_CHECK(state.dim() == 2 && state.size(1) == 8, op, ": state must be [N, 8]");
+  const int64_t N = state.size(0), A1 = bh.numel();
+  TORCH_CHECK(k >= 1 && out.numel() == N * k * 84 * 84 && prev.numel() == out.numel() &&
+                  prev.data_ptr() != out.data_ptr(),
+              op, ": frame stacks prev / out are distinct [N, k, 84, 84] buffers");
+  TORCH_CHECK(t.numel() == N && tg.numel() == N && ep_ret.numel() == N && ids.numel() == N, op,
+              ": t, tg, ep_ret and env_ids must be [N]");
+  TORCH_CHECK(A1 >= 1 && Wh.numel() == 512 * A1, op, ": bad head shapes (Wh [512, A + 1], bh [A + 1])");
+  TORCH_CHECK(E <= INT32_MAX && N <= INT32_MAX, op, ": counts must fit 32 bits");
+  aca::PongIO io{};
+  io.state = ptr<float>(state);
+  io.tsteps = ptr<int32_t>(t);
+  io.tglob = ptr<int64_t>(tg);
+  io.ep_ret = ptr<float>(ep_ret);
+  io.env_ids = ptr<int64_t>(ids);
+  io.prev = ptr<uint8_t>(prev);
+  io.out = ptr<uint8_t>(out);
+  io.seed = (uint32_t)seed;
+  io.max_steps = (int)max_steps;
+  io.k = (int)k;
+  if (has(reward)) {
+    need(*reward, at::kFloat, "reward");
+    TORCH_CHECK(reward->numel() >= N, op, ": reward must hold N values");
+    io.reward = ptr<float>(*reward);
+  }
+  if (has(done)) {
+    need(*done, at::kByte, "done");
+    TORCH_CHECK(done->numel() >= N, op, ": done must hold N values");
+    io.done_out = ptr<uint8_t>(*done);
+  }
+  aca::PolicyArgs pol{};
+  if (has(h)) {
+    need(*h, at::kBFloat16, "h");
+    TORCH_CHECK(h->numel() == N * 512, op, ": h must be [N, 512]");
+    pol.h = ptr<uint16_t>(*h);
+  }
+  pol.Wh = ptr<uint16_t>(Wh);
+  pol.bh = ptr<float>(bh);
+  pol.A = (int)A1 - 1;
+  if (has(act)) {
+    need(*act, at::kInt, "act");
+    TORCH_CHECK(act->numel() >= N, op, ": act must hold N values");
+    pol.act = ptr<int32_t>(*act);
+  }
+  const aca::FcParts fc = fc_parts(op, hpart, planes, bfc, N);
+  aca::PongEvalRec rec{};
+  rec.E = (int)E;
+  const int64_t need_slots = N * (E > 0 ? E : 0);
+  if (has(rec_ret)) {
+    need(*rec_ret, at::kFloat, "rec_ret");
+    TORCH_CHECK(rec_ret->numel() >= need_slots, op, ": rec_ret must be [N, E]");
+    rec.ep_ret = ptr<float>(*rec_ret);
+  }
+  if (has(rec_len)) {
+    need(*rec_len, at::kInt, "rec_len");
+    TORCH_CHECK(rec_len->numel() >= need_slots, op, ": rec_len must be [N, E]");
+    rec.ep_len = ptr<int32_t>(*rec_len);
+  }
+  if (has(rec_cnt)) {
+    need(*rec_cnt, at::kInt, "rec_cnt");
+    TORCH_CHECK(rec_cnt->numel() >= N, op, ": rec_cnt must be [N]");
+    rec.cnt = ptr<int32_t>(*rec_cnt);
+  }
+  check(aca_env_policy_eval_pong(&io, &fc, &pol, &rec, 512, (int)N, pre_shifted ? 1 : 0, cur_stream(state)), op);
+}
+
 // Rollout step t of the Pong bank fused with the row-split trunk of the observation it produces (cnn_fused.hip
 // pong_fused_step_kernel): env state read from (state, t, tg, ep_ret), committed to the other parity buffers
 // (state_n, t_n, tg_n, ep_ret_n); prev = obs[t], out = obs[t+1] (frames 0..2 already shifted in), shift_out =
@@ -2276,6 +2361,10 @@ TORCH_LIBRARY(acamd, m) {
         "Tensor env_ids, Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor truncated, int seed, "
         "int max_steps, int k, bool pre_shifted=False, Tensor? hpart=None, int planes=0, Tensor? bfc=None, "
         "Tensor? stamps=None) -> ()");
+  m.def("env_policy_eval_pong(Tensor? h, Tensor Wh, Tensor bh, Tensor state, Tensor t, Tensor tg, Tensor ep_ret, "
+        "Tensor env_ids, Tensor prev, Tensor out, int seed, int max_steps, int k, bool pre_shifted, Tensor? hpart, "
+        "int planes, Tensor? bfc, Tensor? rec_ret, Tensor? rec_len, Tensor? rec_cnt, int E, Tensor? act=None, "
+        "Tensor? reward=None, Tensor? done=None) -> ()");
   m.def("fc_value(Tensor hpart, int planes, Tensor bfc, Tensor Wh, Tensor bh, Tensor out, Tensor? h_out) -> ()");
   m.def("pong_fused_step(Tensor h, Tensor Wh, Tensor bh, Tensor z, Tensor act, Tensor logp, Tensor ent, "
         "Tensor value, int key_shift, int pseed, Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor state_n, "
@@ -2417,6 +2506,7 @@ TORCH_LIBRARY_IMPL(acamd, CUDA, m) {
   m.impl("env_step_linear", &env_step_linear);
   m.impl("env_step_pong", &env_step_pong);
   m.impl("env_policy_step_pong", &env_policy_step_pong);
+  m.impl("env_policy_eval_pong", &env_policy_eval_pong);
   m.impl("pong_fused_step", &pong_fused_step);
   m.impl("categorical_sample", &categorical_sample);
   m.impl("gaussian_sample", &gaussian_sample);

@@ -36,6 +36,15 @@ struct PongIO {
   int k;                 // the fused steps fix it at 4: set by the launcher there
 };
 
+// Episode records of a deterministic evaluation (env_atari.hip pong_policy_eval_kernel; ops/evaluation.py
+// EvalRecords): the first E finished episodes of every env, written by the env's own workgroup as they end.
+struct PongEvalRec {
+  float* ep_ret;     // [N, E]
+  int32_t* ep_len;   // [N, E]
+  int32_t* cnt;      // [N]
+  int E;
+};
+
 struct PongNext {   // the next parity's env state buffers (written by the committing workgroup)
   float* state;
   int32_t* tsteps;

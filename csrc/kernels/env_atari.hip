@@ -122,6 +122,95 @@ __global__ void __launch_bounds__(256) pong_policy_step_kernel(PongIO io, FcPart
   }
 }
 
+// Deterministic evaluation step (algos/evaluator.py path "cnn"): the same hidden row, head GEMV, three physics
+// candidates, shift and render as pong_policy_step_kernel, a kernel of its own so that the rollout step keeps its
+// code. The action is the first index of the largest of the A logits (argmax_step's tie rule = torch.argmax's; a NaN
+// logit never wins, all-NaN gives 0: the GREEDY categorical head of mlp.hip) over the 8-lane trees -- no key is
+// hashed, no expf / logf, and h, z, log-prob, entropy and value are not stored. The commit advances state / t / tg /
+// ep_ret exactly as pong_commit but leaves the bank's ep_stats alone; a finished episode goes to the env's next free
+// record slot (ops/evaluation.py eval_scan_ref semantics). act / reward / done columns are optional.
+__device__ __forceinline__ void pong_commit_eval(const PongIO& io, const PongEvalRec& rec, int e, const PongOut& r,
+                                                 int64_t tg_old) {
+  io.tglob[e] = tg_old + 1;
+  if (io.reward) io.reward[e] = r.rew;
+  if (io.done_out) io.done_out[e] = r.done;
+  if (r.done) {
+    const int c = rec.cnt[e];
+    if (c >= 0 && c < rec.E) {
+      rec.ep_ret[(size_t)e * rec.E + c] = r.er;
+      rec.ep_len[(size_t)e * rec.E + c] = r.t;
+      rec.cnt[e] = c + 1;
+    }
+  }
+  io.tsteps[e] = r.done ? 0 : r.t;
+  io.ep_ret[e] = r.done ? 0.0f : r.er;
+  float* sp = io.state + (size_t)e * 8;
+  const PongState& s = r.s;
+  sp[0] = s.bx; sp[1] = s.by; sp[2] = s.vx; sp[3] = s.vy; sp[4] = s.pa; sp[5] = s.po; sp[6] = s.sa; sp[7] = s.so;
+}
+
+template <int A1>
+__global__ void __launch_bounds__(256) pong_policy_eval_kernel(PongIO io, FcParts fc, const u16* __restrict__ h,
+                                                               const u16* __restrict__ Wh,
+                                                               const float* __restrict__ bh,
+                                                               int32_t* __restrict__ act, PongEvalRec rec,
+                                                               int pre_shifted) {
+  constexpr int A = A1 - 1;
+  static_assert(A1 >= 3 && A1 <= 8, "the arg-max runs on the 8-lane trees");
+  const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  __shared__ int sh_act;
+  __shared__ PongOut cand[3];
+  __shared__ float s_acc[4][A1];
+  const int64_t tg0 = io.tglob[e];
+  const float bhj = bh[lane < A1 ? lane : 0];
+  uint32_t wv[A1];
+#pragma unroll
+  for (int u = 0; u < A1; ++u) wv[u] = reinterpret_cast<const uint32_t*>(Wh)[A1 * tid + u];
+  float hf[2];
+  if (fc.hpart) {
+    fc_h2_from_parts(fc.hpart, fc.S, fc.plane_stride, fc.bfc, e, tid, nullptr, hf);   // h is not stored
+  } else {
+    const uint32_t hw = reinterpret_cast<const uint32_t*>(h + (size_t)e * HEAD_HDIM)[tid];
+    hf[0] = __uint_as_float(hw << 16);
+    hf[1] = __uint_as_float(hw & 0xFFFF0000u);
+  }
+  if (tid >= 64 && tid < 67) cand[tid - 64] = pong_advance(io, e, (float)(tid - 65));
+  float acc[A1];
+#pragma unroll
+  for (int j = 0; j < A1; ++j) {
+    // Wh[2t][j] and Wh[2t+1][j] are elements j and A1 + j of the thread's 2 * A1 bf16
+    const uint32_t w0 = wv[j >> 1], w1 = wv[(A1 + j) >> 1];
+    const float a0 = __uint_as_float((j & 1) ? (w0 & 0xFFFF0000u) : (w0 << 16));
+    const float a1 = __uint_as_float(((A1 + j) & 1) ? (w1 & 0xFFFF0000u) : (w1 << 16));
+    acc[j] = wave_sum(hf[0] * a0 + hf[1] * a1);
+  }
+  if (lane == 0)
+#pragma unroll
+    for (int j = 0; j < A1; ++j) s_acc[wid][j] = acc[j];
+  __syncthreads();
+  if (wid == 0) {
+    const int jj = lane < A1 ? lane : 0;
+    const float zj = ((s_acc[0][jj] + s_acc[1][jj]) + (s_acc[2][jj] + s_acc[3][jj])) + bhj;
+    // lanes >= A (the value column included) and NaN logits hold the arg-max's neutral element
+    const bool on = lane < A;
+    float best = (on && zj == zj) ? zj : -INFINITY;
+    int bi = on ? lane : 1 << 30;
+    argmax_step(best, bi, xor4f(best), xor4i(bi));
+    argmax_step(best, bi, xor2f(best), xor2i(bi));
+    argmax_step(best, bi, xor1f(best), xor1i(bi));
+    if (lane == 0) {
+      if (act) act[e] = bi;
+      sh_act = bi;
+    }
+  } else if (!pre_shifted) {
+    pong_shift(io, e, 64, blockDim.x - 64);   // else the trunk kernel already shifted the stack
+  }
+  __syncthreads();
+  const PongOut& r = cand[pong_dir_index(sh_act)];
+  if (tid == 0) pong_commit_eval(io, rec, e, r, tg0);
+  pong_render(io, e, r.s, r.done != 0);
+}
+
 }  // namespace aca
 
 extern "C" hipError_t aca_env_step_pong(const aca::PongIO* io, const int32_t* actions, int N, hipStream_t stream) {
@@ -151,6 +240,32 @@ extern "C" hipError_t aca_env_policy_step_pong(const aca::PongIO* io, const aca:
     ACA_POLICY_CASE(13) ACA_POLICY_CASE(14) ACA_POLICY_CASE(15) ACA_POLICY_CASE(16) ACA_POLICY_CASE(17)
     ACA_POLICY_CASE(18) ACA_POLICY_CASE(19) ACA_POLICY_CASE(20)
 #undef ACA_POLICY_CASE
+    default:
+      return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+extern "C" hipError_t aca_env_policy_eval_pong(const aca::PongIO* io, const aca::FcParts* fc,
+                                               const aca::PolicyArgs* pol, const aca::PongEvalRec* rec, int hdim,
+                                               int N, int pre_shifted, hipStream_t stream) {
+  const aca::PolicyArgs& p = *pol;
+  if (hdim != aca::HEAD_HDIM || !p.Wh || !p.bh || reinterpret_cast<uintptr_t>(p.Wh) % 16 ||
+      reinterpret_cast<uintptr_t>(p.h) % 16 || (!fc->hpart && !p.h))
+    return hipErrorInvalidValue;
+  if (fc->hpart && (fc->S < 1 || fc->S > aca::FC_MAX_PLANES || !fc->bfc || reinterpret_cast<uintptr_t>(fc->hpart) % 16 ||
+                    reinterpret_cast<uintptr_t>(fc->bfc) % 16 || fc->plane_stride % 4))
+    return hipErrorInvalidValue;
+  if (rec->E < 1 || !rec->ep_ret || !rec->ep_len || !rec->cnt) return hipErrorInvalidValue;
+  if (p.A + 1 < 3 || p.A + 1 > 8 || io->k < 1) return hipErrorInvalidValue;
+  if (N <= 0) return hipSuccess;
+  switch (p.A + 1) {
+#define ACA_EVAL_CASE(A1)                                                                                          \
+  case A1:                                                                                                         \
+    aca::pong_policy_eval_kernel<A1><<<N, 256, 0, stream>>>(*io, *fc, p.h, p.Wh, p.bh, p.act, *rec, pre_shifted);  \
+    break;
+    ACA_EVAL_CASE(3) ACA_EVAL_CASE(4) ACA_EVAL_CASE(5) ACA_EVAL_CASE(6) ACA_EVAL_CASE(7) ACA_EVAL_CASE(8)
+#undef ACA_EVAL_CASE
     default:
       return hipErrorInvalidValue;
   }

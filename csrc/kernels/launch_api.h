@@ -35,6 +35,12 @@ hipError_t aca_env_step_linear(const aca::EnvIO* io, const float* actions, const
 hipError_t aca_env_step_pong(const aca::PongIO* io, const int32_t* actions, int N, hipStream_t stream);
 hipError_t aca_env_policy_step_pong(const aca::PongIO* io, const aca::FcParts* fc, const aca::PolicyArgs* pol,
                                     int hdim, int N, int pre_shifted, uint64_t* stamps, hipStream_t stream);
+// deterministic evaluation step: arg-max action, env step, episode records. Of pol only h (read when fc has no
+// planes), Wh, bh, A and the optional act column are used; io.reward / io.done_out are optional columns, io.ep_stats
+// and io.trunc_out are not touched. A + 1 in 3..8, rec.E >= 1.
+hipError_t aca_env_policy_eval_pong(const aca::PongIO* io, const aca::FcParts* fc, const aca::PolicyArgs* pol,
+                                    const aca::PongEvalRec* rec, int hdim, int N, int pre_shifted,
+                                    hipStream_t stream);
 
 // ---- Nature-CNN engine (cnn_fused.hip, fc_rollout.hip, fc_bwd.hip, conv_wgrad.hip)
 // fused rollout steps: io.k set by the launcher; nx = the other parity's env state (aca_pong_fused_env_step: null

@@ -82,16 +82,23 @@ def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None
             "ppo": {"epochs": cfg.ppo_epochs, "minibatches": cfg.ppo_minibatches} if cfg.algo == "ppo" else None}
 
 
-def run_eval(name, reps, device, norm_obs=False, eval_envs=16, eval_episodes=1):
+def run_eval(name, reps, device, norm_obs=False, eval_envs=16, eval_episodes=1, max_episode_steps=None, opts=None):
     """The deterministic evaluation of a config (``TrainConfig.eval_every``; algos/evaluator.py) on its own: time per
-    evaluation as its captured graph replays (restore, launches, summary), and, as the yardstick of the fused path, the
-    training rollout (``collect``: rollout launch + critic launch) timed eagerly on the same trainer."""
+    evaluation as its captured graph replays (restore, launches, summary; the CNN path: its chain of chunk graphs),
+    and, as the yardstick, the training rollout (``collect``) timed eagerly on the same trainer.
+    ``max_episode_steps``: the time limit of both banks (the evaluation runs ``eval_episodes`` times as many steps)."""
+    from actor_critic_algs_on_tensorflow_amd import envs as E
     from actor_critic_algs_on_tensorflow_amd import preset
     from actor_critic_algs_on_tensorflow_amd.algos.trainer import ActorCriticTrainer
     cuda = device.startswith("cuda")
+    kw = dict(engine_opts=opts) if opts else {}
     cfg = preset(name, device=device, outdir=None, quiet=True, stdout_freq=0, save_every=0, cuda_graph=cuda,
-                 eval_every=1, eval_envs=eval_envs, eval_episodes=eval_episodes, norm_obs=norm_obs)
-    tr = ActorCriticTrainer(cfg)
+                 eval_every=1, eval_envs=eval_envs, eval_episodes=eval_episodes, norm_obs=norm_obs, **kw)
+    env = None
+    if max_episode_steps is not None:
+        env = E.make(cfg.env, cfg.num_envs, device=device, seed=cfg.seed, max_episode_steps=int(max_episode_steps),
+                     frame_stack=4 if ("Pong" in cfg.env or "Breakout" in cfg.env) else cfg.frames)
+    tr = ActorCriticTrainer(cfg, env=env)
     ev = tr.evaluator
 
     def timed(fn, n):
@@ -140,13 +147,18 @@ def main():
     ap.add_argument("--target-kl", type=float, default=None,
                     help="set TrainConfig.target_kl on the chosen configs (PPO; early stopping on the approximate KL)")
     ap.add_argument("--eval", action="store_true",
-                    help="measure the deterministic evaluation (eval_every) of the chosen MLP configs instead of their "
-                         "updates: --updates replays of the evaluation graph (--norm-obs: with the normaliser)")
+                    help="measure the deterministic evaluation (eval_every) of the chosen configs (the MLP presets and "
+                         "pong_a2c / breakout_ppo) instead of their updates: --updates replays of the evaluation graph "
+                         "(--norm-obs: with the normaliser; --engine-opts reaches the CNN engine)")
+    ap.add_argument("--eval-envs", type=int, default=16, help="--eval: envs of the evaluation bank")
+    ap.add_argument("--eval-max-steps", type=int, default=None,
+                    help="--eval: time limit of the banks = steps of one evaluation (default: the env's own)")
     args = ap.parse_args()
     opts = json.loads(args.engine_opts) if args.engine_opts else None
     if args.eval:
         for name in args.configs.split(","):
-            res = run_eval(name, args.updates, args.device, args.norm_obs)
+            res = run_eval(name, args.updates, args.device, args.norm_obs, args.eval_envs,
+                           max_episode_steps=args.eval_max_steps, opts=opts)
             os.write(out_fd, (json.dumps(res) + "\n").encode())
         return
     for name in args.configs.split(","):
