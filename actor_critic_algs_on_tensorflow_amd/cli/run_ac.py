@@ -15,7 +15,9 @@ import os
 def build_parser():
     p = argparse.ArgumentParser(formatter_class=argparse.ArgumentDefaultsHelpFormatter)
     p.add_argument("--animate", default=False, action="store_true")
-    p.add_argument("--env", default="Pendulum-v0")
+    p.add_argument("--env", default="Pendulum-v0",
+                   help="env id (envs.REGISTRY): CartPole-v0 / -v1, Pendulum-v0, Acrobot-v1, MountainCar-v0, "
+                        "MountainCarContinuous-v0, PongNoFrameskip-v4, BreakoutNoFrameskip-v4, HalfCheetahShape-v0")
     p.add_argument("--seed", default=12321, type=int)
     p.add_argument("--tboard", default=False, action="store_true")
     p.add_argument("--save_every", default=600, type=int)

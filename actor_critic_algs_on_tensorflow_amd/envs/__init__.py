@@ -8,7 +8,8 @@ from __future__ import annotations
 
 from .atari import BreakoutShapeVecEnv, PongVecEnv
 from .base import VecEnv
-from .classic import CartPoleV0VecEnv, CartPoleVecEnv, PendulumVecEnv
+from .classic import (AcrobotVecEnv, CartPoleV0VecEnv, CartPoleVecEnv, MountainCarContinuousVecEnv, MountainCarVecEnv,
+                      PendulumVecEnv)
 from .mujoco import MujocoShapeVecEnv
 from .spaces import Box, Discrete, EnvSpec
 
@@ -17,6 +18,9 @@ REGISTRY = {
     "CartPole-v1": CartPoleVecEnv,
     "Pendulum-v0": PendulumVecEnv,
     "Pendulum-v1": PendulumVecEnv,
+    "Acrobot-v1": AcrobotVecEnv,
+    "MountainCar-v0": MountainCarVecEnv,
+    "MountainCarContinuous-v0": MountainCarContinuousVecEnv,
     "PongNoFrameskip-v4": PongVecEnv,
     "Pong": PongVecEnv,
     "BreakoutNoFrameskip-v4": BreakoutShapeVecEnv,
@@ -54,4 +58,5 @@ def get_roll_params(env_id, variant="basic"):
 
 
 __all__ = ["make", "get_roll_params", "REGISTRY", "VecEnv", "Box", "Discrete", "EnvSpec", "PongVecEnv",
-           "CartPoleVecEnv", "PendulumVecEnv", "MujocoShapeVecEnv", "BreakoutShapeVecEnv", "CartPoleV0VecEnv"]
+           "CartPoleVecEnv", "PendulumVecEnv", "MujocoShapeVecEnv", "BreakoutShapeVecEnv", "CartPoleV0VecEnv",
+           "AcrobotVecEnv", "MountainCarVecEnv", "MountainCarContinuousVecEnv"]

@@ -136,6 +136,39 @@ void env_step_linear(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep
         "env_step_linear");
 }
 
+void env_step_acrobot(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids, Tensor actions,
+                      Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc, int64_t seed,
+                      int64_t max_steps, int64_t k, c10::optional<Tensor> final_out) {
+  const aca::EnvIO io = env_io("acrobot", 6, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed,
+                               max_steps, k, final_out);
+  need(actions, at::kInt, "actions");
+  TORCH_CHECK(state.size(1) == 4 && actions.numel() == io.N, "acrobot env: bad shapes");
+  check(aca_env_step_acrobot(&io, ptr<int32_t>(actions), cur_stream(state)), "env_step_acrobot");
+}
+
+void env_step_mountaincar(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids,
+                          Tensor actions, Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc,
+                          int64_t seed, int64_t max_steps, int64_t k, c10::optional<Tensor> final_out) {
+  const aca::EnvIO io = env_io("mountaincar", 2, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc,
+                               seed, max_steps, k, final_out);
+  need(actions, at::kInt, "actions");
+  TORCH_CHECK(state.size(1) == 2 && actions.numel() == io.N, "mountaincar env: bad shapes");
+  check(aca_env_step_mountaincar(&io, ptr<int32_t>(actions), cur_stream(state)), "env_step_mountaincar");
+}
+
+void env_step_mountaincar_cont(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids,
+                               Tensor actions, Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc,
+                               int64_t seed, int64_t max_steps, int64_t k, c10::optional<Tensor> final_out) {
+  const aca::EnvIO io = env_io("mountaincar_cont", 2, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done,
+                               trunc, seed, max_steps, k, final_out);
+  need(actions, at::kFloat, "actions");
+  TORCH_CHECK(state.size(1) == 2 && io.N > 0 && actions.numel() >= io.N && actions.numel() % io.N == 0,
+              "mountaincar_cont env: bad shapes");
+  const int act_dim = actions.numel() / io.N;
+  check(aca_env_step_mountaincar_cont(&io, ptr<float>(actions), act_dim, cur_stream(state)),
+        "env_step_mountaincar_cont");
+}
+
 // The validated operands of a Pong-shaped bank step: state [N, 8], frame stacks [N, k, 84, 84] uint8. prev = nullptr
 // (the fused per-env step): one stack, read and written in place.
 aca::PongIO pong_io(const char* op, const Tensor& state, const Tensor& t, const Tensor& tg, const Tensor& ep_ret,
@@ -2353,6 +2386,15 @@ TORCH_LIBRARY(acamd, m) {
   m.def("env_step_linear(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, "
         "Tensor actions, Tensor A, Tensor B, Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor truncated, "
         "int seed, int max_steps, int k, Tensor? final_out=None) -> ()");
+  m.def("env_step_acrobot(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, "
+        "Tensor actions, Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor truncated, int seed, "
+        "int max_steps, int k, Tensor? final_out=None) -> ()");
+  m.def("env_step_mountaincar(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, "
+        "Tensor actions, Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor truncated, int seed, "
+        "int max_steps, int k, Tensor? final_out=None) -> ()");
+  m.def("env_step_mountaincar_cont(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, "
+        "Tensor env_ids, Tensor actions, Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor truncated, "
+        "int seed, int max_steps, int k, Tensor? final_out=None) -> ()");
   m.def("env_step_pong(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, "
         "Tensor actions, Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor truncated, int seed, "
         "int max_steps, int k) -> ()");
@@ -2504,6 +2546,9 @@ TORCH_LIBRARY_IMPL(acamd, CUDA, m) {
   m.impl("env_step_cartpole", &env_step_cartpole);
   m.impl("env_step_pendulum", &env_step_pendulum);
   m.impl("env_step_linear", &env_step_linear);
+  m.impl("env_step_acrobot", &env_step_acrobot);
+  m.impl("env_step_mountaincar", &env_step_mountaincar);
+  m.impl("env_step_mountaincar_cont", &env_step_mountaincar_cont);
   m.impl("env_step_pong", &env_step_pong);
   m.impl("env_policy_step_pong", &env_policy_step_pong);
   m.impl("env_policy_eval_pong", &env_policy_eval_pong);

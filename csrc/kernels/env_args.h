@@ -1,4 +1,4 @@
-// Argument blocks of the env-bank kernels (env_classic.hip, env_atari.hip, cnn_fused.hip), shared with
+// Argument blocks of the env-bank kernels (env_classic.hip, env_gym.hip, env_atari.hip, cnn_fused.hip), shared with
 // csrc/bindings.cpp: plain C types only, so both hipcc and g++ compile this header. The binding fills them by field
 // name; the kernels take them by value.
 #pragma once
@@ -6,7 +6,7 @@
 
 namespace aca {
 
-// vector-observation banks (CartPole, Pendulum, the linear-Gaussian system)
+// vector-observation banks (CartPole, Pendulum, Acrobot, MountainCar, the linear-Gaussian system)
 struct EnvIO {
   float* state;
   int32_t* t;
