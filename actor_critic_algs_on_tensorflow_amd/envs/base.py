@@ -156,7 +156,12 @@ class VecEnv:
             new = torch.cat([prev[:, d:], frame.to(out.dtype)], dim=1)
         out.copy_(new)
 
-    native_final_obs = False   # env kernel writes the terminal observation (subclasses with that support)
+    native_op = None   # a vector bank's ``torch.ops.acamd`` step op (``csrc/kernels/env_classic.hip``)
+
+    @property
+    def native_final_obs(self):
+        """The env kernel can write the terminal observation (time-limit bootstrap): every vector bank's does."""
+        return self.native_op is not None
 
     def step(self, actions, prev_obs=None, obs_out=None, reward_out=None, done_out=None, trunc_out=None,
              final_out=None):
@@ -223,8 +228,14 @@ class VecEnv:
         self._stack_push(f, prev, out)
         self._stack_reset(f, out, done)
 
-    def _native_step(self, actions, prev, out, rew, done, trunc):
-        raise NotImplementedError(f"{type(self).__name__} has no native kernel")
+    def _native_step(self, actions, prev, out, rew, done, trunc, final_out=None):
+        if self.native_op is None:
+            raise NotImplementedError(f"{type(self).__name__} has no native kernel")
+        a = actions.to(torch.int32) if self.is_discrete else actions.reshape(self.num_envs, -1).float().contiguous()
+        getattr(_native.require(), self.native_op)(
+            self.state, self.t, self.tg, self.ep_ret, self.ep_stats, self.env_ids, a,
+            prev, out, rew, done, trunc, self.seed, self.max_episode_steps, self.frame_stack,
+            final_out)
 
     def drain_episode_stats(self):
         """Host read of (mean finished return, episodes, mean length) since the last drain (syncs)."""

@@ -12,8 +12,8 @@
   goal minus ``0.1 u^2`` of the unclipped action.
 
 CartPole and Pendulum are the envs the reference trains on (``README.md``, ``Basic_AC/run_AC.py:13``). Random resets
-use the counter-based hash RNG (:mod:`.rng`) so the HIP kernels (``csrc/kernels/env_classic.hip``, and
-``csrc/kernels/env_gym.hip`` for Acrobot and the MountainCar tasks) reproduce them.
+use the counter-based hash RNG (:mod:`.rng`) so the HIP kernels (``csrc/kernels/env_classic.hip``: one task struct per
+env around one bank-step kernel, launched by :meth:`VecEnv._native_step` through ``native_op``) reproduce them.
 """
 from __future__ import annotations
 
@@ -21,7 +21,6 @@ import math
 
 import torch
 
-from .. import _native
 from . import rng
 from .base import VecEnv
 from .spaces import Box, Discrete
@@ -29,6 +28,7 @@ from .spaces import Box, Discrete
 
 class CartPoleVecEnv(VecEnv):
     env_id = "CartPole-v1"
+    native_op = "env_step_cartpole"
     state_dim = 4
     default_max_steps = 500
     observation_space = Box(low=[-4.8, -3.4e38, -0.419, -3.4e38], high=[4.8, 3.4e38, 0.419, 3.4e38])
@@ -69,14 +69,6 @@ class CartPoleVecEnv(VecEnv):
     def _frame(self):
         return self.state.clone()
 
-    native_final_obs = True   # the kernel can write the terminal observation (time-limit bootstrap)
-
-    def _native_step(self, actions, prev, out, rew, done, trunc, final_out=None):
-        _native.require().env_step_cartpole(
-            self.state, self.t, self.tg, self.ep_ret, self.ep_stats, self.env_ids, actions.to(torch.int32),
-            prev, out, rew, done, trunc, self.seed, self.max_episode_steps, self.frame_stack,
-            final_out)
-
 
 class CartPoleV0VecEnv(CartPoleVecEnv):
     env_id = "CartPole-v0"
@@ -89,6 +81,7 @@ def angle_normalize(x):
 
 class PendulumVecEnv(VecEnv):
     env_id = "Pendulum-v0"
+    native_op = "env_step_pendulum"
     state_dim = 2
     default_max_steps = 200
     observation_space = Box(low=[-1.0, -1.0, -8.0], high=[1.0, 1.0, 8.0])
@@ -122,15 +115,6 @@ class PendulumVecEnv(VecEnv):
         th, thdot = self.state.unbind(1)
         return torch.stack([torch.cos(th), torch.sin(th), thdot], 1)
 
-    native_final_obs = True   # the kernel can write the terminal observation (time-limit bootstrap)
-
-    def _native_step(self, actions, prev, out, rew, done, trunc, final_out=None):
-        _native.require().env_step_pendulum(
-            self.state, self.t, self.tg, self.ep_ret, self.ep_stats, self.env_ids,
-            actions.reshape(self.num_envs, -1).float().contiguous(),
-            prev, out, rew, done, trunc, self.seed, self.max_episode_steps, self.frame_stack,
-            final_out)
-
 
 def _f32(x):
     """The fp32 value of a constant as a Python float: comparisons against it are exact in either precision."""
@@ -156,6 +140,7 @@ def _wrap(x, lo, hi):
 
 class AcrobotVecEnv(VecEnv):
     env_id = "Acrobot-v1"
+    native_op = "env_step_acrobot"
     state_dim = 4
     default_max_steps = 500
     observation_space = Box(low=[-1.0, -1.0, -1.0, -1.0, -4 * math.pi, -9 * math.pi],
@@ -216,17 +201,10 @@ class AcrobotVecEnv(VecEnv):
         th1, th2, w1, w2 = self.state.unbind(1)
         return torch.stack([torch.cos(th1), torch.sin(th1), torch.cos(th2), torch.sin(th2), w1, w2], 1)
 
-    native_final_obs = True   # the kernel can write the terminal observation (time-limit bootstrap)
-
-    def _native_step(self, actions, prev, out, rew, done, trunc, final_out=None):
-        _native.require().env_step_acrobot(
-            self.state, self.t, self.tg, self.ep_ret, self.ep_stats, self.env_ids, actions.to(torch.int32),
-            prev, out, rew, done, trunc, self.seed, self.max_episode_steps, self.frame_stack,
-            final_out)
-
 
 class MountainCarVecEnv(VecEnv):
     env_id = "MountainCar-v0"
+    native_op = "env_step_mountaincar"
     state_dim = 2
     default_max_steps = 200
     observation_space = Box(low=[-1.2, -0.07], high=[0.6, 0.07])
@@ -264,17 +242,10 @@ class MountainCarVecEnv(VecEnv):
     def _frame(self):
         return self.state.clone()
 
-    native_final_obs = True   # the kernel can write the terminal observation (time-limit bootstrap)
-
-    def _native_step(self, actions, prev, out, rew, done, trunc, final_out=None):
-        _native.require().env_step_mountaincar(
-            self.state, self.t, self.tg, self.ep_ret, self.ep_stats, self.env_ids, actions.to(torch.int32),
-            prev, out, rew, done, trunc, self.seed, self.max_episode_steps, self.frame_stack,
-            final_out)
-
 
 class MountainCarContinuousVecEnv(MountainCarVecEnv):
     env_id = "MountainCarContinuous-v0"
+    native_op = "env_step_mountaincar_cont"
     default_max_steps = 999
     action_space = Box(low=[-1.0], high=[1.0])
 
@@ -286,10 +257,3 @@ class MountainCarContinuousVecEnv(MountainCarVecEnv):
         term = self._move(torch.clamp(u, -1.0, 1.0))
         # the action penalty reads the unclipped action (gym Continuous_MountainCarEnv.step)
         return torch.where(term, torch.full_like(u, 100.0), torch.zeros_like(u)) - (u * u) * 0.1, term
-
-    def _native_step(self, actions, prev, out, rew, done, trunc, final_out=None):
-        _native.require().env_step_mountaincar_cont(
-            self.state, self.t, self.tg, self.ep_ret, self.ep_stats, self.env_ids,
-            actions.reshape(self.num_envs, -1).float().contiguous(),
-            prev, out, rew, done, trunc, self.seed, self.max_episode_steps, self.frame_stack,
-            final_out)

@@ -66,7 +66,7 @@ class MujocoShapeVecEnv(VecEnv):
     def _frame(self):
         return self.state.clone()
 
-    native_final_obs = True   # the kernel can write the terminal observation (time-limit bootstrap)
+    native_op = "env_step_linear"   # called below, not by VecEnv._native_step: it takes A and B too
 
     def _native_step(self, actions, prev, out, rew, done, trunc, final_out=None):
         _native.require().env_step_linear(

@@ -103,23 +103,28 @@ aca::EnvIO env_io(const char* op, int64_t D, const Tensor& state, const Tensor& 
   return io;
 }
 
-void env_step_cartpole(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids, Tensor actions,
-                       Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc, int64_t seed,
-                       int64_t max_steps, int64_t k, c10::optional<Tensor> final_out) {
-  const aca::EnvIO io = env_io("cartpole", 4, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed,
-                               max_steps, k, final_out);
-  need(actions, at::kInt, "actions");
-  check(aca_env_step_cartpole(&io, ptr<int32_t>(actions), cur_stream(state)), "env_step_cartpole");
-}
+// The one-thread-per-env tasks (env_classic.hip), indexed by aca::EnvTask: state width S, frame width D, action dtype
+struct BankTask { const char* op; int64_t S, D; at::ScalarType act; };
+const BankTask BANK_TASKS[] = {{"env_step_cartpole", 4, 4, at::kInt},
+                               {"env_step_pendulum", 2, 3, at::kFloat},
+                               {"env_step_acrobot", 4, 6, at::kInt},
+                               {"env_step_mountaincar", 2, 2, at::kInt},
+                               {"env_step_mountaincar_cont", 2, 2, at::kFloat}};
 
-void env_step_pendulum(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids, Tensor actions,
-                       Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc, int64_t seed,
-                       int64_t max_steps, int64_t k, c10::optional<Tensor> final_out) {
-  const aca::EnvIO io = env_io("pendulum", 3, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed,
-                               max_steps, k, final_out);
-  need(actions, at::kFloat, "actions");
-  const int act_dim = actions.numel() / io.N;
-  check(aca_env_step_pendulum(&io, ptr<float>(actions), act_dim, cur_stream(state)), "env_step_pendulum");
+// actions: [N] int32 for the discrete tasks, [N, act_dim] float (column 0 drives the env) for the continuous ones
+template <aca::EnvTask TASK>
+void env_step_bank(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids, Tensor actions,
+                   Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc, int64_t seed, int64_t max_steps,
+                   int64_t k, c10::optional<Tensor> final_out) {
+  const BankTask& task = BANK_TASKS[TASK];
+  const aca::EnvIO io = env_io(task.op, task.D, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc,
+                               seed, max_steps, k, final_out);
+  need(actions, task.act, "actions");
+  const int64_t N = io.N, na = actions.numel();
+  TORCH_CHECK(state.dim() == 2 && state.size(1) == task.S && N > 0 && na >= N && na % N == 0 &&
+                  (task.act == at::kFloat || na == N),
+              task.op, ": bad shapes");
+  check(aca_env_step_bank(TASK, &io, actions.data_ptr(), (int)(na / N), cur_stream(state)), task.op);
 }
 
 void env_step_linear(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids, Tensor actions,
@@ -134,39 +139,6 @@ void env_step_linear(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep
               "linear env: bad shapes");
   check(aca_env_step_linear(&io, ptr<float>(actions), ptr<float>(A), ptr<float>(B), cur_stream(state)),
         "env_step_linear");
-}
-
-void env_step_acrobot(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids, Tensor actions,
-                      Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc, int64_t seed,
-                      int64_t max_steps, int64_t k, c10::optional<Tensor> final_out) {
-  const aca::EnvIO io = env_io("acrobot", 6, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc, seed,
-                               max_steps, k, final_out);
-  need(actions, at::kInt, "actions");
-  TORCH_CHECK(state.size(1) == 4 && actions.numel() == io.N, "acrobot env: bad shapes");
-  check(aca_env_step_acrobot(&io, ptr<int32_t>(actions), cur_stream(state)), "env_step_acrobot");
-}
-
-void env_step_mountaincar(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids,
-                          Tensor actions, Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc,
-                          int64_t seed, int64_t max_steps, int64_t k, c10::optional<Tensor> final_out) {
-  const aca::EnvIO io = env_io("mountaincar", 2, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done, trunc,
-                               seed, max_steps, k, final_out);
-  need(actions, at::kInt, "actions");
-  TORCH_CHECK(state.size(1) == 2 && actions.numel() == io.N, "mountaincar env: bad shapes");
-  check(aca_env_step_mountaincar(&io, ptr<int32_t>(actions), cur_stream(state)), "env_step_mountaincar");
-}
-
-void env_step_mountaincar_cont(Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor ids,
-                               Tensor actions, Tensor prev, Tensor out, Tensor reward, Tensor done, Tensor trunc,
-                               int64_t seed, int64_t max_steps, int64_t k, c10::optional<Tensor> final_out) {
-  const aca::EnvIO io = env_io("mountaincar_cont", 2, state, t, tg, ep_ret, ep_stats, ids, prev, out, reward, done,
-                               trunc, seed, max_steps, k, final_out);
-  need(actions, at::kFloat, "actions");
-  TORCH_CHECK(state.size(1) == 2 && io.N > 0 && actions.numel() >= io.N && actions.numel() % io.N == 0,
-              "mountaincar_cont env: bad shapes");
-  const int act_dim = actions.numel() / io.N;
-  check(aca_env_step_mountaincar_cont(&io, ptr<float>(actions), act_dim, cur_stream(state)),
-        "env_step_mountaincar_cont");
 }
 
 // The validated operands of a Pong-shaped bank step: state [N, 8], frame stacks [N, k, 84, 84] uint8. prev = nullptr
@@ -2543,12 +2515,12 @@ TORCH_LIBRARY(acamd, m) {
 }
 
 TORCH_LIBRARY_IMPL(acamd, CUDA, m) {
-  m.impl("env_step_cartpole", &env_step_cartpole);
-  m.impl("env_step_pendulum", &env_step_pendulum);
+  m.impl("env_step_cartpole", &env_step_bank<aca::ENV_CARTPOLE>);
+  m.impl("env_step_pendulum", &env_step_bank<aca::ENV_PENDULUM>);
   m.impl("env_step_linear", &env_step_linear);
-  m.impl("env_step_acrobot", &env_step_acrobot);
-  m.impl("env_step_mountaincar", &env_step_mountaincar);
-  m.impl("env_step_mountaincar_cont", &env_step_mountaincar_cont);
+  m.impl("env_step_acrobot", &env_step_bank<aca::ENV_ACROBOT>);
+  m.impl("env_step_mountaincar", &env_step_bank<aca::ENV_MOUNTAINCAR>);
+  m.impl("env_step_mountaincar_cont", &env_step_bank<aca::ENV_MOUNTAINCAR_CONT>);
   m.impl("env_step_pong", &env_step_pong);
   m.impl("env_policy_step_pong", &env_policy_step_pong);
   m.impl("env_policy_eval_pong", &env_policy_eval_pong);

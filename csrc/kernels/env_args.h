@@ -1,4 +1,4 @@
-// Argument blocks of the env-bank kernels (env_classic.hip, env_gym.hip, env_atari.hip, cnn_fused.hip), shared with
+// Argument blocks of the env-bank kernels (env_classic.hip, env_atari.hip, cnn_fused.hip), shared with
 // csrc/bindings.cpp: plain C types only, so both hipcc and g++ compile this header. The binding fills them by field
 // name; the kernels take them by value.
 #pragma once
@@ -26,6 +26,9 @@ struct EnvIO {
   int k;
   int N;
 };
+
+// the one-thread-per-env tasks of env_classic.hip (aca_env_step_bank)
+enum EnvTask { ENV_CARTPOLE, ENV_PENDULUM, ENV_ACROBOT, ENV_MOUNTAINCAR, ENV_MOUNTAINCAR_CONT };
 
 // Pong-shaped banks (state [N, 8], frame stacks [N, k, 84, 84] uint8)
 struct PongIO {

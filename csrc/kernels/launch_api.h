@@ -27,16 +27,13 @@
 
 extern "C" {
 
-// ---- env banks (env_classic.hip, env_gym.hip, env_atari.hip)
-hipError_t aca_env_step_cartpole(const aca::EnvIO* io, const int32_t* actions, hipStream_t stream);
-hipError_t aca_env_step_pendulum(const aca::EnvIO* io, const float* actions, int act_dim, hipStream_t stream);
+// ---- env banks (env_classic.hip, env_atari.hip)
+// gym classic control, one thread per env: actions are [N, act_dim] of the task's action type (int32 with act_dim = 1
+// for the discrete tasks, else float), column 0 drives the env
+hipError_t aca_env_step_bank(aca::EnvTask task, const aca::EnvIO* io, const void* actions, int act_dim,
+                             hipStream_t stream);
 hipError_t aca_env_step_linear(const aca::EnvIO* io, const float* actions, const float* A, const float* B,
                                hipStream_t stream);
-// gym classic control (env_gym.hip); continuous actions are [N, act_dim], column 0 drives the env
-hipError_t aca_env_step_acrobot(const aca::EnvIO* io, const int32_t* actions, hipStream_t stream);
-hipError_t aca_env_step_mountaincar(const aca::EnvIO* io, const int32_t* actions, hipStream_t stream);
-hipError_t aca_env_step_mountaincar_cont(const aca::EnvIO* io, const float* actions, int act_dim,
-                                         hipStream_t stream);
 hipError_t aca_env_step_pong(const aca::PongIO* io, const int32_t* actions, int N, hipStream_t stream);
 hipError_t aca_env_policy_step_pong(const aca::PongIO* io, const aca::FcParts* fc, const aca::PolicyArgs* pol,
                                     int hdim, int N, int pre_shifted, uint64_t* stamps, hipStream_t stream);

@@ -37,6 +37,7 @@
 
 #include "common.h"
 #include "launch_api.h"
+#include "linear_env.h"
 
 namespace aca {
 
@@ -1493,35 +1494,11 @@ __global__ void __launch_bounds__(256) mlp_tshadow_kernel(const MlpTower* __rest
 // "a persistent rollout kernel for the MLP configs"). One workgroup owns 16 envs for all T steps:
 //   actor forward (layer_fwd; the transposed weight shadows stay hot in this CU's L2 across steps) -> Gaussian sample /
 //   log-prob / entropy (the mode-0 head of mlp_fwd_kernel, same RNG keys) -> env step by 32-lane groups (the
-//   arithmetic of env_classic.hip linear_step_kernel, fma contraction off) -> frame-stack push straight into the LDS
+//   arithmetic linear_env.h shares with env_classic.hip linear_step_kernel) -> frame-stack push straight into the LDS
 //   observation tile of the next step (double-buffered).
 // Env state, step counters and episode returns live in LDS for the whole rollout (read once, written back once); the
 // observation slab, actions, log-probs, entropies, rewards and done flags stream out. The critic's values of all
 // (T+1)*N observations are one batched mlp_fwd launch afterwards (ops/mlp.py), off this serial chain.
-constexpr int LIN_OBS = 17, LIN_ACT = 6, LIN_LANES = 32;
-
-__device__ __forceinline__ float lin_row(const float* s, const float* av, const float* sA, const float* sB, int r,
-                                         float nz) {
-#pragma clang fp contract(off)
-  float acc = 0.f, acc2 = 0.f;
-  for (int c = 0; c < LIN_OBS; ++c) acc += s[c] * sA[r * LIN_OBS + c];
-  for (int c = 0; c < LIN_ACT; ++c) acc2 += av[c] * sB[r * LIN_ACT + c];
-  return acc + acc2 + (nz - 0.5f) * 0.02f;
-}
-__device__ __forceinline__ float lin_asq(const float* av) {
-#pragma clang fp contract(off)
-  float asq = 0.f;
-  for (int j = 0; j < LIN_ACT; ++j) asq += av[j] * av[j];
-  return asq;
-}
-__device__ __forceinline__ float lin_reward(float y8, float asq) {
-#pragma clang fp contract(off)
-  return y8 - 0.1f * asq;
-}
-__device__ __forceinline__ float lin_reset(float u) {
-#pragma clang fp contract(off)
-  return (u - 0.5f) * 0.2f;
-}
 
 // The rollout's tile is ROLL_RB = 4 envs: its per-step chain is bound by the f32 MFMA work of ONE CU (16 env rows on
 // 16x16x4 tiles: 0.86 MFLOP = 3.4k clocks per step at the CU's 256 FLOP/clk, ~4.5 of 6.3 us measured), so 4-env

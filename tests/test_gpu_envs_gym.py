@@ -1,4 +1,4 @@
-"""Acrobot-v1, MountainCar-v0 and MountainCarContinuous-v0 on an MI355X: the env kernels of csrc/kernels/env_gym.hip
+"""Acrobot-v1, MountainCar-v0 and MountainCarContinuous-v0 on an MI355X: their tasks of csrc/kernels/env_classic.hip
 against their torch oracles (envs/classic.py), planted goal / wall states on the device, the native MLP engine on
 the three banks against the torch engine, and the ``acrobot_ppo`` preset learning on the native engine."""
 import math

@@ -128,10 +128,15 @@ def test_im2col_col2im(cuda):
 
 
 # ------------------------------------------------------------------------------------------------------ env banks
-@pytest.mark.parametrize("env_id", ["PongNoFrameskip-v4", "CartPole-v1", "Pendulum-v0", "HalfCheetahShape-v0"])
-def test_env_bank_matches_oracle(cuda, env_id):
+@pytest.mark.parametrize("env_id,N", [
+    pytest.param(i, 16, id=i) for i in ["PongNoFrameskip-v4", "CartPole-v1", "Pendulum-v0", "HalfCheetahShape-v0"]
+] + [pytest.param(i, 300, id=i + "-300") for i in ["CartPole-v1", "Pendulum-v0"]])
+def test_env_bank_matches_oracle(cuda, env_id, N):
+    """N = 300 runs a second, partly filled workgroup of the one-thread-per-env bank step. The done flags of two fp32
+    banks that may differ by ulps are compared exactly: with these seeds CartPole at N = 300 ends 730 episodes in the
+    60 steps on the CPU oracle, and no pre-reset x or theta comes closer than 2.5e-5 to its threshold, against a
+    one-step difference of 2.4e-7 at most (the banks are re-synced after every step)."""
     from actor_critic_algs_on_tensorflow_amd import envs as E
-    N = 16
     gpu = E.make(env_id, N, device=cuda, seed=5)
     cpu = E.make(env_id, N, device="cpu", seed=5)
     gpu.reset()
@@ -158,15 +163,18 @@ def test_env_bank_matches_oracle(cuda, env_id):
     assert torch.allclose(cpu.ep_stats, gpu.ep_stats.cpu(), rtol=1e-4, atol=1e-3)
 
 
-@pytest.mark.parametrize("env_id", ["CartPole-v1", "Pendulum-v0", "HalfCheetahShape-v0"])
-def test_env_bank_final_obs_matches_oracle(cuda, env_id):
+@pytest.mark.parametrize("env_id,frame_stack", [
+    pytest.param(i, 1, id=i) for i in ["CartPole-v1", "Pendulum-v0", "HalfCheetahShape-v0"]
+] + [pytest.param("Pendulum-v0", 3, id="Pendulum-v0-stack3")])
+def test_env_bank_final_obs_matches_oracle(cuda, env_id, frame_stack):
     """The optional terminal-observation output of the vector-observation env kernels (final_out: the stack holding
     the transition's new frame before any auto-reset) == the torch oracle's, on two envs with a 3-step time limit so
-    that every third step resets; same oracle and tolerances as test_env_bank_matches_oracle."""
+    that every third step resets; same oracle and tolerances as test_env_bank_matches_oracle. Pendulum's frame is the
+    one odd width (3), run with a stack of 3 too."""
     from actor_critic_algs_on_tensorflow_amd import envs as E
     N = 2
-    gpu = E.make(env_id, N, device=cuda, seed=5, max_episode_steps=3)
-    cpu = E.make(env_id, N, device="cpu", seed=5, max_episode_steps=3)
+    gpu = E.make(env_id, N, device=cuda, seed=5, max_episode_steps=3, frame_stack=frame_stack)
+    cpu = E.make(env_id, N, device="cpu", seed=5, max_episode_steps=3, frame_stack=frame_stack)
     assert gpu.native_final_obs
     for bank in (gpu, cpu):
         bank.keep_final_obs = True
@@ -189,6 +197,34 @@ def test_env_bank_final_obs_matches_oracle(cuda, env_id):
         gpu.state.copy_(cpu.state)
         gpu.obs.copy_(cpu.obs)
     assert resets >= 2
+
+
+@pytest.mark.parametrize("env_id", ["CartPole-v1", "Pendulum-v0"])
+def test_env_bank_op_rejects_bad_shapes(cuda, env_id):
+    """The bank-step binding refuses, before any launch, a state of the wrong width and an action tensor shorter than
+    the bank (a GPU test: the ops refuse CPU tensors before they look at shapes)."""
+    from actor_critic_algs_on_tensorflow_amd import _native
+    from actor_critic_algs_on_tensorflow_amd import envs as E
+    N = 2
+    env = E.make(env_id, N, device=cuda, seed=5)
+    env.reset()
+    op = getattr(_native.require(), env.native_op)
+    a = env.sample_actions()
+    a = a.to(torch.int32) if env.is_discrete else a.reshape(N, -1).float().contiguous()
+
+    def call(state, actions):
+        op(state, env.t, env.tg, env.ep_ret, env.ep_stats, env.env_ids, actions, env.obs.clone(), env.obs, env.reward,
+           env.done, env.truncated, env.seed, env.max_episode_steps, env.frame_stack, None)
+
+    before = env.tg.clone()
+    wide = torch.zeros(N, env.state_dim + 1, device=cuda)
+    with pytest.raises(RuntimeError, match="bad shapes"):
+        call(wide, a)
+    with pytest.raises(RuntimeError, match="bad shapes"):
+        call(env.state, a[:N - 1].contiguous())
+    assert torch.equal(env.tg, before)   # nothing ran
+    call(env.state, a)
+    assert torch.equal(env.tg, before + 1)
 
 
 # ------------------------------------------------------------------------------------------------------ heads / returns
