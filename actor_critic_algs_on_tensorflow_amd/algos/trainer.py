@@ -144,6 +144,8 @@ class ActorCriticTrainer:
             self._check_norm_reward()
         if cfg.target_kl is not None:
             self._check_target_kl()
+        if cfg.ep_window or cfg.stop_return is not None:
+            self._check_ep_window()
         if cfg.eval_every:
             self._check_eval()
         if dp is not None:
@@ -224,6 +226,15 @@ class ActorCriticTrainer:
         if cfg.norm_reward:
             from ..ops.reward_norm import RewardNormalizer
             self.reward_norm = RewardNormalizer(N, cfg.gamma, cfg.reward_clip, 1e-8, self.device)
+        # rolling window over the last ep_window finished training episodes (ops/ep_monitor.py): every collect variant
+        # feeds it st.rewards / st.dones right after the rollout wrote them raw (in front of the reward scaling and of
+        # any bootstrap term), inside the captured update and on its one stream; it writes nothing the trainer reads
+        self.ep_monitor = None
+        self.stopped_at = None   # the update after which stop_return ended train()
+        self._ep_last = None
+        if cfg.ep_window:
+            from ..ops.ep_monitor import EpisodeMonitor
+            self.ep_monitor = EpisodeMonitor(N, cfg.ep_window, self.device).reserve(T)
         dev = self.device
         self.ent_coef = torch.tensor(cfg.ent_coef, device=dev)
         self.kl_coef = torch.tensor(cfg.kl_coef, device=dev)
@@ -316,6 +327,24 @@ class ActorCriticTrainer:
             raise ValueError(f"norm_reward=True with algo={self.cfg.algo!r}: the reference-parity trainers (a3c, "
                              "basic_ac) keep the reference's raw rewards; use a2c or ppo")
 
+    def _check_ep_window(self):
+        """``ep_window`` covers a2c / ppo (under data parallelism every rank keeps the window of its own envs and no
+        collective is issued); ``stop_return`` reads the window at log time on one rank."""
+        cfg = self.cfg
+        if not 0 <= int(cfg.ep_window) <= 4096:
+            raise ValueError(f"ep_window={cfg.ep_window}: must be in 0 .. 4096 (episodes; 0 = off)")
+        if cfg.ep_window and cfg.algo not in ("a2c", "ppo"):
+            raise ValueError(f"ep_window with algo={cfg.algo!r}: the reference-parity trainers (a3c, basic_ac) keep the "
+                             "reference's episode logging; use a2c or ppo")
+        if cfg.stop_return is not None:
+            if not cfg.ep_window or not cfg.stdout_freq:
+                raise ValueError("stop_return needs ep_window > 0 and stdout_freq > 0: the threshold is compared with "
+                                 "the window's mean return where a log row is produced")
+            if self.dp is not None:
+                raise ValueError("stop_return under data parallelism: every rank would have to take the same stop "
+                                 "decision from its own window, and sharing it between ranks is not built yet; run on "
+                                 "one rank or leave stop_return=None")
+
     def _check_target_kl(self):
         """``target_kl`` covers PPO on one rank: the torch engine (any model) and the native MLP engine."""
         from ..models.policy import CNNActorCritic
@@ -378,6 +407,15 @@ class ActorCriticTrainer:
         st = self.storage
         self.reward_norm.update_(st.rewards, st.dones, self.dp, self._comm)
 
+    def _raw_rewards_ready(self):
+        """Every collect variant calls this once per update, when ``st.rewards`` holds the raw env rewards of the whole
+        rollout: the episode window first (it only reads), then the reward scaling."""
+        if self.ep_monitor is not None:
+            st = self.storage
+            self.ep_monitor.update(st.rewards, st.dones)
+        if self.reward_norm is not None:
+            self._scale_rewards()
+
     def _nobs(self, obs):
         """Torch engine: what a tower reads for the raw observations ``obs``."""
         return obs if self.obs_norm is None else self.obs_norm.apply(obs)
@@ -434,12 +472,15 @@ class ActorCriticTrainer:
         if self.mlp is not None:
             return self._collect_mlp()
         if self.engine is not None:
-            return self._collect_native()
+            self._collect_native()
+            if self.ep_monitor is not None:   # (no reward scaling or bootstrap on the CNN engine: st.rewards stay raw)
+                self._raw_rewards_ready()
+            return
         st, env, model = self.storage, self.env, self.model
-        # reward scaling: the scan sees raw env rewards only, so the per-step bootstrap terms (critic units: already
-        # scaled) wait in a side buffer and are added after the scaling
+        # reward scaling / the episode window: their scans see raw env rewards only, so the per-step bootstrap terms
+        # (critic units: already scaled) wait in a side buffer and are added afterwards (the same fp32 add per element)
         side = None
-        if self.reward_norm is not None and self.cfg.bootstrap_on_timeout:
+        if (self.reward_norm is not None or self.ep_monitor is not None) and self.cfg.bootstrap_on_timeout:
             side = getattr(self, "_boot_side", None)
             if side is None:
                 side = self._boot_side = torch.zeros_like(st.rewards)
@@ -462,10 +503,9 @@ class ActorCriticTrainer:
                     st.rewards[t].add_(self.cfg.gamma * vf * st.truncated[t].to(vf.dtype))
                 else:
                     side[t].copy_(self.cfg.gamma * vf * st.truncated[t].to(vf.dtype))
-        if self.reward_norm is not None:
-            self._scale_rewards()
-            if side is not None:
-                st.rewards.add_(side)
+        self._raw_rewards_ready()
+        if side is not None:
+            st.rewards.add_(side)
         st.values[st.T].copy_(model.value(self._nobs(st.obs[st.T])))
 
     @torch.no_grad()
@@ -481,7 +521,8 @@ class ActorCriticTrainer:
             # critic launch over the slots and one fix-up launch put gamma * V(terminal observation) into the rewards
             eng.rollout_linear(env, st, KEY_ENV_BITS, self.policy_seed,
                                boot=self._timeout_boot_ws() if boot else None,
-                               after_rollout=self._scale_rewards if self.reward_norm is not None else None)
+                               after_rollout=self._raw_rewards_ready
+                               if self.reward_norm is not None or self.ep_monitor is not None else None)
             return
         if boot and getattr(self, "_final_obs", None) is None:
             self._final_obs = torch.zeros((st.T,) + tuple(st.obs.shape[1:]), dtype=st.obs.dtype, device=self.device)
@@ -493,8 +534,7 @@ class ActorCriticTrainer:
                      done_out=st.dones[t], trunc_out=st.truncated[t],
                      final_out=self._final_obs[t] if boot else None)
         eng.value(st.obs[st.T], st.values[st.T])
-        if self.reward_norm is not None:
-            self._scale_rewards()   # raw env rewards; the bootstrap term below is added unscaled
+        self._raw_rewards_ready()   # raw env rewards; the bootstrap term below is added unscaled
         if boot:
             # a time-limit cut stays an episode boundary (done = 1); the truncated step's reward gets
             # gamma * V(terminal observation): ONE critic launch over the T x N terminal stacks the env kernel wrote
@@ -1529,12 +1569,27 @@ class ActorCriticTrainer:
             # any did) and the optimiser steps the update applied, for the metrics stream only
             s["approx_kl"] = vals[STAT_KEYS.index("approx_kl")]
             s["ppo_steps"] = int(vals[STAT_KEYS.index("ppo_steps")])
+        if self.ep_monitor is not None:
+            s.update(self._read_ep_window())
         if self._kl_deferred():
             # DP + global advantage normalisation: this row's kl is rank 0's local post-update KL and act_lr the value
             # before the KL-adaptive rule, which settles inside the NEXT update's moments all-reduce (_kl_deferred);
             # the lr sequence used for training is the single-GPU one, the logged columns lag it by one update
             s["kl_lr_presettle"] = 1
         return s
+
+    def _read_ep_window(self):
+        """The episode window's summary as metrics columns: the one host read the window costs per log row (also what
+        ``stop_return`` is compared with)."""
+        v = self.ep_monitor.summary.detach().cpu().tolist()
+        self._ep_last = dict(ep_ret_mean=v[2], ep_ret_std=v[3], ep_ret_min=v[4], ep_ret_max=v[5], ep_len_mean=v[6],
+                             ep_count=int(v[0]), ep_total=int(v[1]), ep_new=int(v[7]))
+        return self._ep_last
+
+    def _stop_return_met(self):
+        """At a log row, on the read it made: the window is full and its mean return reached ``stop_return``."""
+        ep = self._ep_last
+        return ep["ep_count"] == self.cfg.ep_window and ep["ep_ret_mean"] >= self.cfg.stop_return
 
     def check_health(self, collective=False):
         """Raises if a native in-launch hand-off timed out (its outputs, and so this update's gradients, would be
@@ -1566,6 +1621,7 @@ class ActorCriticTrainer:
             self._maybe_fault()
             self.step()
             it = self.iteration - 1
+            stop = False
             if self.evaluator is not None and it % cfg.eval_every == 0:
                 self._eval_row(it)
             if cfg.stdout_freq and it % cfg.stdout_freq == 0:
@@ -1576,6 +1632,10 @@ class ActorCriticTrainer:
                     extra = {"phase_ms": self.timer.summary()} if cfg.trace else {}
                     self.logger.log_metrics(iteration=it, env_steps=self.env_steps,
                                             env_steps_per_sec=self.env_steps / max(el, 1e-9), **extra, **s)
+                if self.ep_monitor is not None and s is None and (self.tb is not None or cfg.stop_return is not None):
+                    self._read_ep_window()   # (no Logger row was written: the read it would have made)
+                if cfg.stop_return is not None:
+                    stop = self._stop_return_met()
                 if self.tb is not None:
                     self.tb.write(it, extra=self._tb_scalars(s))
                 if cfg.mode.startswith("debug") and (cfg.mode != "debug-light" or self.rank == 0):
@@ -1587,6 +1647,9 @@ class ActorCriticTrainer:
                 self.save_checkpoint()
             if callback is not None:
                 callback(self, it)
+            if stop:   # stop_return: the usual end-of-train flushes and health check still run
+                self.stopped_at = it
+                break
         self.flush_pending()
         self.flush_kl()
         self.check_health(collective=True)
@@ -1636,7 +1699,10 @@ class ActorCriticTrainer:
         if s is None:
             vals = self.stats_buf.detach().cpu().tolist()
             s = {k: vals[STAT_KEYS.index(k)] for k in LOG_KEYS}
-        return {"train/" + k: float(v) for k, v in s.items() if isinstance(v, (int, float))}
+        ep = self._ep_last if self.ep_monitor is not None and self._ep_last is not None else {}
+        out = {"train/" + k: float(v) for k, v in s.items() if isinstance(v, (int, float)) and k not in ep}
+        out.update({"rollout/" + k: float(v) for k, v in ep.items()})   # the episode window (ep_window)
+        return out
 
     @torch.no_grad()
     def _debug_print(self):

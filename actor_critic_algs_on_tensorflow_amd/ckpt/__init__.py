@@ -19,7 +19,9 @@ This module writes and reads the same files through the C++ codec (:mod:`.codec`
   optimiser moments/step/lr per group, iteration and env-step counters, env-bank state, and -- for a ``norm_obs``
   trainer -- the observation normaliser as fp64 tensors ``_acamd/obs_norm/{count,mean,m2,clip}``; for a ``norm_reward``
   trainer the reward scaler's statistics as fp64 ``_acamd/reward_norm/{count,mean,m2,clip,gamma}`` and its per-env
-  running return as fp64 ``reward_ret`` beside the env-bank tensors (per rank). TF ignores unknown
+  running return as fp64 ``reward_ret`` beside the env-bank tensors (per rank); for an ``ep_window`` trainer the episode
+  window ``_acamd/ep_monitor/{cur_ret,cur_len,ring_ret,ring_len,total}`` in its own dtypes (per rank, gathered with the
+  env banks: ``_acamd/ep_monitor/rank<r>/...`` under data parallelism). TF ignores unknown
   keys only if they are not requested, so reference tooling can still restore the model variables.
 
 A ``checkpoint`` state file (``model_checkpoint_path: "..."``) is written next to the bundles and the newest
@@ -149,6 +151,18 @@ REWARD_NORM_PREFIX = "_acamd/reward_norm/"
 _REWARD_NORM_KEYS = ("count", "mean", "m2", "clip", "gamma")
 
 
+EP_MONITOR_PREFIX = "_acamd/ep_monitor/"
+_EP_MONITOR_KEYS = ("cur_ret", "cur_len", "ring_ret", "ring_len", "total")
+_EP = "ep_monitor/"   # the window's tensors among a rank's env-bank tensors
+
+
+def _rank_key(k, rank=None):
+    """The bundle key of a per-rank tensor: the episode window under its own prefix, everything else beside the env
+    banks."""
+    r = f"rank{rank}/" if rank is not None else ""
+    return EP_MONITOR_PREFIX + r + k[len(_EP):] if k.startswith(_EP) else "_acamd/env/" + r + k
+
+
 def _env_tensor(k, v):
     """A gathered env-bank tensor as it is stored: the reward scaler's returns as numpy float64 (``_to_np`` would
     store a floating tensor as fp32 and break bit-exact resume)."""
@@ -162,6 +176,10 @@ def _env_state(trainer):
     rn = getattr(trainer, "reward_norm", None)
     if rn is not None:   # the per-env running discounted return: local to the rank, like the bank
         st[REWARD_RET] = rn.ret
+    em = getattr(trainer, "ep_monitor", None)
+    if em is not None:   # the episode window: every rank keeps its own
+        for k, v in em.state_dict().items():
+            st[_EP + k] = v
     return st
 
 
@@ -251,11 +269,11 @@ def save_trainer(trainer, path=None):
     tensors["_acamd/iteration"] = np.asarray(trainer.iteration, dtype=np.int64)
     tensors["_acamd/env_steps"] = np.asarray(trainer.env_steps, dtype=np.int64)
     for k, v in envs[0].items():
-        tensors[f"_acamd/env/{k}"] = _env_tensor(k, v)
+        tensors[_rank_key(k)] = _env_tensor(k, v)
     if len(envs) > 1:
         for r, st in envs.items():
             for k, v in st.items():
-                tensors[f"_acamd/env/rank{r}/{k}"] = _env_tensor(k, v)
+                tensors[_rank_key(k, r)] = _env_tensor(k, v)
     tensors["_acamd/world_size"] = np.asarray(len(envs), dtype=np.int64)
     tensors["_acamd/update_counter"] = trainer.update_counter
     tensors["_acamd/ent_coef"] = trainer.ent_coef
@@ -358,6 +376,14 @@ def load_trainer(trainer, path):
                            "norm_reward=True trainer restores (it was written with norm_reward=False)")
         sd["ret"] = torch.as_tensor(np.array(t[pre + REWARD_RET], dtype=np.float64))
         rn.load_state_dict(sd)
+    em = getattr(trainer, "ep_monitor", None)
+    if em is not None:   # (an ep_window=0 trainer ignores the tensors)
+        epre = EP_MONITOR_PREFIX + (f"rank{rank}/" if saved > 1 else "")
+        for k in _EP_MONITOR_KEYS:
+            if epre + k not in t:
+                raise KeyError(f"checkpoint {path} lacks the episode window tensor {epre + k} that an ep_window > 0 "
+                               "trainer restores (it was written with ep_window=0)")
+        em.load_state_dict({k: torch.as_tensor(np.array(t[epre + k])) for k in _EP_MONITOR_KEYS})
     if "_acamd/iteration" in t:
         trainer.iteration = int(t["_acamd/iteration"])
         trainer.env_steps = int(t["_acamd/env_steps"])

@@ -44,6 +44,12 @@ def build_parser():
     p.add_argument("--eval-every", default=0, type=int,
                    help="deterministic evaluation on a second bank after every N-th update (TrainConfig.eval_every; "
                         "--algo a2c|ppo, MLP models, one device)")
+    p.add_argument("--ep-window", default=0, type=int,
+                   help="rolling window over the last K finished training episodes, kept on the device "
+                        "(TrainConfig.ep_window; --algo a2c|ppo): ep_ret_mean, ... in the metrics stream")
+    p.add_argument("--stop-return", default=None, type=float,
+                   help="stop once the episode window is full and its mean return reaches this "
+                        "(TrainConfig.stop_return; needs --ep-window, one device)")
     return p
 
 
@@ -69,6 +75,10 @@ def main(argv=None):
         kw["target_kl"] = a.target_kl
     if a.eval_every:
         kw["eval_every"] = a.eval_every
+    if a.ep_window:
+        kw["ep_window"] = a.ep_window
+    if a.stop_return is not None:
+        kw["stop_return"] = a.stop_return
     cfg = preset(name, **kw)
     res = train(cfg)
     print("done: %d iterations, %d env steps, %.1f env-steps/s" % (res.iterations, res.env_steps,

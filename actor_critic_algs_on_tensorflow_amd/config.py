@@ -140,6 +140,18 @@ class TrainConfig:
     eval_envs: int = 16
     eval_episodes: int = 1
     eval_seed: int | None = None      # None: derived from seed (and different from it)
+    # -- training-time episode statistics ------------------------------------------------------------------------------
+    # rolling window over the last ep_window finished training episodes (ops/ep_monitor.py), kept on the device: after
+    # each rollout the raw rewards / dones are walked in step order per env (a plain fp32 add, carried across updates)
+    # and the finished episodes enter a ring in the order (step, env index); mean / std / min / max of the window are
+    # reduced on the device in a fixed order, so a run repeats them bit for bit. Raw rewards: before norm_reward scales
+    # them and before any bootstrap term. Read once per log row (ep_ret_mean, ... in the metrics stream); nothing the
+    # trainer reads is written. a2c / ppo; under data parallelism every rank keeps the window of its own envs and
+    # rank 0 logs its own. 0 = off, at most 4096
+    ep_window: int = 0
+    # stop training once the window is full and its mean return is >= stop_return (checked where a log row is
+    # produced, so it needs ep_window > 0 and stdout_freq > 0; one rank only). trainer.stopped_at = that update
+    stop_return: float | None = None
     # -- execution -----------------------------------------------------------------------------------------------
     dtype: str = "bf16"               # compute dtype of the GPU engine (fp32 masters always)
     engine: str = "auto"              # auto | native (hand-written HIP engine) | torch (autograd reference)
@@ -230,6 +242,18 @@ class TrainConfig:
         if int(self.eval_envs) < 1 or int(self.eval_episodes) < 1:
             raise ValueError(f"TrainConfig.eval_envs={self.eval_envs}, eval_episodes={self.eval_episodes}: both must "
                              "be >= 1")
+        if not 0 <= int(self.ep_window) <= 4096:
+            raise ValueError(f"TrainConfig.ep_window={self.ep_window}: must be in 0 .. 4096 (episodes; 0 = off)")
+        if self.ep_window and self.algo in ("a3c", "basic_ac"):
+            raise ValueError(f"TrainConfig.ep_window with algo={self.algo!r}: the reference-parity trainers keep the "
+                             "reference's episode logging; use a2c or ppo")
+        if self.stop_return is not None:
+            if not self.ep_window:
+                raise ValueError("TrainConfig.stop_return needs ep_window > 0: the threshold is compared with the mean "
+                                 "return of the episode window")
+            if not self.stdout_freq:
+                raise ValueError("TrainConfig.stop_return needs stdout_freq > 0: the window is read where a log row is "
+                                 "produced")
         if self.look_ahead is not None and int(self.look_ahead) < 1:
             raise ValueError(f"TrainConfig.look_ahead={self.look_ahead}: must be >= 1 (None = the whole rollout)")
 

@@ -1594,6 +1594,66 @@ void reward_norm_apply(Tensor rewards, Tensor tables, double clip) {
   check(aca_reward_norm_apply(&a, cur_stream(rewards)), "reward_norm_apply");
 }
 
+// ---------------------------------------------------------------------------------------------- episode window
+// rewards: fp32 [T, N] raw; dones: uint8 [T, N]; cur_ret fp32 [N], cur_len int32 [N]; ring_ret fp32 [K], ring_len int32
+// [K]; total int64 [1]; summary fp64 [10]; ep_ret fp32 / ep_len int32: scratch of at least T N elements
+// (ep_monitor_args.h; oracle: ops/ep_monitor.py). Two launches: the per-env scan, then the one-workgroup commit.
+int64_t ep_monitor_unroll() { return aca_ep_monitor_unroll(); }
+int64_t ep_monitor_max_cells() { return aca_ep_monitor_max_cells(); }
+
+void ep_monitor_update(Tensor rewards, Tensor dones, Tensor cur_ret, Tensor cur_len, Tensor ring_ret, Tensor ring_len,
+                       Tensor total, Tensor summary, Tensor ep_ret, Tensor ep_len) {
+  for (const Tensor* t : {&rewards, &dones, &cur_ret, &cur_len, &ring_ret, &ring_len, &total, &summary, &ep_ret, &ep_len})
+    TORCH_CHECK(t->is_cuda() && t->device() == rewards.device(), "ep_monitor_update: every operand on one GPU");
+  TORCH_CHECK(rewards.scalar_type() == at::kFloat && rewards.dim() == 2, "ep_monitor_update: rewards must be fp32 "
+              "[T, N], got ", rewards.scalar_type(), " with ", rewards.dim(), " dims");
+  TORCH_CHECK(dones.scalar_type() == at::kByte && dones.dim() == 2 && dones.sizes() == rewards.sizes(),
+              "ep_monitor_update: dones must be uint8 [T, N] like rewards, got ", dones.scalar_type());
+  TORCH_CHECK(rewards.is_contiguous() && dones.is_contiguous(), "ep_monitor_update: rewards and dones must be "
+              "contiguous [T, N]");
+  const int64_t T = rewards.size(0), N = rewards.size(1), K = ring_ret.numel();
+  TORCH_CHECK(T >= 1 && N >= 1 && N < INT32_MAX && T * N <= aca_ep_monitor_max_cells(),
+              "ep_monitor_update: T >= 1, N >= 1 and T N <= ", aca_ep_monitor_max_cells(), " (the commit is one "
+              "workgroup), got T = ", T, ", N = ", N);
+  TORCH_CHECK(K >= 1 && K <= aca_ep_monitor_max_k(), "ep_monitor_update: the window K must be in 1 .. ",
+              aca_ep_monitor_max_k(), ", got ", K);
+  need(cur_ret, at::kFloat, "cur_ret");
+  need(cur_len, at::kInt, "cur_len");
+  need(ring_ret, at::kFloat, "ring_ret");
+  need(ring_len, at::kInt, "ring_len");
+  need(total, at::kLong, "total");
+  need(summary, at::kDouble, "summary");
+  need(ep_ret, at::kFloat, "ep_ret");
+  need(ep_len, at::kInt, "ep_len");
+  TORCH_CHECK(cur_ret.numel() == N && cur_len.numel() == N && ring_len.numel() == K && total.numel() == 1 &&
+                  summary.numel() == 10 && ep_ret.numel() >= T * N && ep_len.numel() >= T * N,
+              "ep_monitor_update: cur_ret / cur_len [N], ring_ret / ring_len [K], total [1], summary [10], ep_ret / "
+              "ep_len of at least T N elements for rewards [T, N]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dones.data_ptr()) % 16 == 0, "ep_monitor_update: dones must be 16-byte "
+              "aligned");
+  aca::EpMonitorScanArgs s{};
+  s.rewards = ptr<float>(rewards);
+  s.dones = ptr<uint8_t>(dones);
+  s.cur_ret = ptr<float>(cur_ret);
+  s.cur_len = ptr<int32_t>(cur_len);
+  s.ep_ret = ptr<float>(ep_ret);
+  s.ep_len = ptr<int32_t>(ep_len);
+  s.T = (int)T;
+  s.N = (int)N;
+  aca::EpMonitorCommitArgs c{};
+  c.dones = s.dones;
+  c.ep_ret = s.ep_ret;
+  c.ep_len = s.ep_len;
+  c.ring_ret = ptr<float>(ring_ret);
+  c.ring_len = ptr<int32_t>(ring_len);
+  c.total = ptr<int64_t>(total);
+  c.summary = ptr<double>(summary);
+  c.cells = T * N;
+  c.K = (int)K;
+  check(aca_ep_monitor_scan(&s, cur_stream(rewards)), "ep_monitor_scan");
+  check(aca_ep_monitor_commit(&c, cur_stream(rewards)), "ep_monitor_commit");
+}
+
 // words: CPU int64 [nseg, 13], fvals: CPU float [nseg, 4] (built once by ops/optim.py FusedGroupStep)
 void opt_multi(Tensor words, Tensor fvals, c10::optional<Tensor> trans, bool adam, double b1, double b2, double eps,
                bool zero_grad, Tensor stream_ref, int64_t t_off) {
@@ -2458,6 +2518,10 @@ TORCH_LIBRARY(acamd, m) {
         "float clip) -> ()");
   m.def("obs_norm_merge(Tensor? part, int nparts, Tensor batch, float nb, Tensor state, Tensor tables, int stage, "
         "float eps) -> ()");
+  m.def("ep_monitor_unroll() -> int", &ep_monitor_unroll);
+  m.def("ep_monitor_max_cells() -> int", &ep_monitor_max_cells);
+  m.def("ep_monitor_update(Tensor rewards, Tensor dones, Tensor cur_ret, Tensor cur_len, Tensor ring_ret, "
+        "Tensor ring_len, Tensor total, Tensor summary, Tensor ep_ret, Tensor ep_len) -> ()");
   m.def("reward_norm_unroll() -> int", &reward_norm_unroll);
   m.def("reward_norm_scan(Tensor rewards, Tensor dones, Tensor ret, Tensor state, Tensor part, float gamma) -> ()");
   m.def("reward_norm_apply(Tensor rewards, Tensor tables, float clip) -> ()");
@@ -2556,6 +2620,7 @@ TORCH_LIBRARY_IMPL(acamd, CUDA, m) {
   m.impl("timeout_bootstrap", &timeout_bootstrap);
   m.impl("obs_norm_prepare", &obs_norm_prepare);
   m.impl("obs_norm_merge", &obs_norm_merge);
+  m.impl("ep_monitor_update", &ep_monitor_update);
   m.impl("reward_norm_scan", &reward_norm_scan);
   m.impl("reward_norm_apply", &reward_norm_apply);
   m.impl("mlp_epoch_gather", &mlp_epoch_gather);

@@ -15,6 +15,7 @@
 
 #include "cnn_args.h"
 #include "env_args.h"
+#include "ep_monitor_args.h"
 #include "eval_scan_args.h"
 #include "gemm_desc.h"
 #include "loss_args.h"
@@ -139,6 +140,13 @@ hipError_t aca_reward_norm_apply(const aca::RewardNormApplyArgs* a, hipStream_t 
 // ---- evaluation records from stored reward / done columns (eval_scan.hip)
 int aca_eval_scan_unroll(void);   // EVS_UNROLL: time steps per load round of the scan
 hipError_t aca_eval_scan(const aca::EvalScanArgs* a, hipStream_t stream);
+
+// ---- rolling window over the last K finished training episodes (ep_monitor.hip)
+int aca_ep_monitor_unroll(void);          // EPM_UNROLL: time steps per load round of the scan
+int aca_ep_monitor_max_k(void);           // EPM_MAX_K
+int64_t aca_ep_monitor_max_cells(void);   // EPM_MAX_CELLS: the largest T N the commit takes
+hipError_t aca_ep_monitor_scan(const aca::EpMonitorScanArgs* a, hipStream_t stream);
+hipError_t aca_ep_monitor_commit(const aca::EpMonitorCommitArgs* a, hipStream_t stream);
 
 // ---- GEMM and explicit conv plumbing (gemm*.hip, conv.hip)
 int aca_gemm_tile_dims(int tile, int* bm, int* bn);

@@ -4,7 +4,7 @@
     python scripts/bench_configs.py [--configs pong_a2c,breakout_ppo,mujoco_ppo_dp8,cartpole_cpu] [--updates K]
                                     [--warmup W] [--engine auto|torch] [--device cuda:0] [--engine-opts JSON]
                                     [--bootstrap-on-timeout] [--norm-obs] [--norm-reward]
-                                    [--target-kl X]
+                                    [--target-kl X] [--ep-window K]
 
 Each config runs with its preset (config.py PRESETS): same model, env bank, rollout length, optimiser and PPO
 epochs/minibatches as BASELINE.json names; synthetic envs and random-init weights. The update is captured as a
@@ -26,7 +26,7 @@ import torch  # noqa: E402
 
 
 def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None, bootstrap_on_timeout=False,
-        norm_obs=False, norm_reward=False, target_kl=None):
+        norm_obs=False, norm_reward=False, target_kl=None, ep_window=0):
     from actor_critic_algs_on_tensorflow_amd import preset
     from actor_critic_algs_on_tensorflow_amd.algos.trainer import ActorCriticTrainer
     dev = device if name != "cartpole_cpu" or device == "cpu" else device
@@ -40,6 +40,8 @@ def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None
         cfg = cfg.replace(norm_reward=True)   # (validated: MLP configs only)
     if target_kl is not None:
         cfg = cfg.replace(target_kl=target_kl)   # (validated: PPO configs only; a CNN config runs on the torch engine)
+    if ep_window:
+        cfg = cfg.replace(ep_window=ep_window)   # (the rolling episode window: two launches per update)
     if engine_opts:
         import dataclasses
         cfg.engine_opts = dataclasses.replace(cfg.engine_opts, **engine_opts)
@@ -78,7 +80,7 @@ def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None
             "engine": "native-cnn" if tr.engine is not None else ("native-mlp" if tr.mlp is not None else "torch"),
             "hipgraph": bool(tr.graph), "device": dev, "dp_world1": bool(dp_world1),
             "engine_opts": engine_opts or {}, "bootstrap_on_timeout": bool(cfg.bootstrap_on_timeout),
-            "norm_obs": bool(cfg.norm_obs), "norm_reward": bool(cfg.norm_reward),
+            "norm_obs": bool(cfg.norm_obs), "norm_reward": bool(cfg.norm_reward), "ep_window": int(cfg.ep_window),
             "ppo": {"epochs": cfg.ppo_epochs, "minibatches": cfg.ppo_minibatches} if cfg.algo == "ppo" else None}
 
 
@@ -146,6 +148,8 @@ def main():
                     help="set TrainConfig.norm_reward on the chosen configs (MLP models)")
     ap.add_argument("--target-kl", type=float, default=None,
                     help="set TrainConfig.target_kl on the chosen configs (PPO; early stopping on the approximate KL)")
+    ap.add_argument("--ep-window", type=int, default=0,
+                    help="set TrainConfig.ep_window on the chosen configs (the rolling window over the last K episodes)")
     ap.add_argument("--eval", action="store_true",
                     help="measure the deterministic evaluation (eval_every) of the chosen configs (the MLP presets and "
                          "pong_a2c / breakout_ppo) instead of their updates: --updates replays of the evaluation graph "
@@ -163,7 +167,7 @@ def main():
         return
     for name in args.configs.split(","):
         res = run(name, args.updates, args.warmup, args.engine, args.device, args.dp_world1, opts,
-                  args.bootstrap_on_timeout, args.norm_obs, args.norm_reward, args.target_kl)
+                  args.bootstrap_on_timeout, args.norm_obs, args.norm_reward, args.target_kl, args.ep_window)
         os.write(out_fd, (json.dumps(res) + "\n").encode())
 
 
