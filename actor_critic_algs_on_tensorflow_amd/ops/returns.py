@@ -16,7 +16,8 @@ env) -- both are affine recurrences ``x_t = a_t + c_t x_{t+1}`` -- together with
 moments a data-parallel run all-reduces, and (optionally) the in-place advantage normalisation. The truncated
 n-step window (``L < T``) uses its prefix-sum form (scan of the un-bootstrapped return + next-terminal index). The
 simple per-column kernels (:func:`gae`, :func:`nstep_returns`) stay as the small-T building blocks. The PyTorch
-code below is the oracle all of them are tested against.
+code below is the oracle all of them are tested against; ``tests/oracles/returns_oracle.py`` is the independent fp64
+oracle (fp32-rounded ``gamma`` / ``lambda``, derived tolerances) that pins every kernel, and this code, at the edges.
 """
 from __future__ import annotations
 
@@ -202,7 +203,9 @@ def returns_scan(rews, vals, dones, mode="gae", gamma=0.99, lam=0.95, look_ahead
     (``[count, sum adv, sum adv^2, sum ret, sum ret^2, sum V, sum V^2, sum ret*V]``, pre-normalisation) and, if
     ``ev_out`` is given, ``ev_out[0]`` = EV correlation of (ret, V[:T]) (``Basic_AC/util.py:4-12``)."""
     T, N = rews.shape
-    L = T if look_ahead is None else int(look_ahead)
+    L = max(T, 1) if look_ahead is None else int(look_ahead)
+    if L < 1:
+        raise ValueError(f"look_ahead must be >= 1 (or None for the whole rollout), got {look_ahead}")
     if not _native.use_native(rews):
         ret, adv = gae_ref(rews, vals, dones, gamma, lam) if mode == "gae" else \
             nstep_returns_ref(rews, vals, dones, gamma, L)

@@ -612,10 +612,17 @@ void gae(Tensor r, Tensor v, Tensor d, Tensor ret, Tensor adv, double gamma, dou
         "gae");
 }
 
+// The n-step look-ahead as the kernels take it: L < 1 would put the window end h = t + L before t (reads before the
+// rollout), so it is refused; a window longer than the rollout is the whole rollout (and t + L stays in int range).
+int look_ahead_arg(const char* op, int64_t L, int64_t T) {
+  TORCH_CHECK(L >= 1, op, ": look_ahead must be >= 1, got ", L);
+  return (int)std::min<int64_t>(L, std::max<int64_t>(T, 1));
+}
+
 void nstep_returns(Tensor r, Tensor v, Tensor d, Tensor tgt, Tensor adv, double gamma, int64_t L) {
   check_returns(r, v, d, tgt, adv);
   check(aca_nstep(ptr<float>(r), ptr<float>(v), ptr<uint8_t>(d), ptr<float>(tgt), ptr<float>(adv), r.size(0),
-                  r.size(1), (float)gamma, (int)L, cur_stream(r)),
+                  r.size(1), (float)gamma, look_ahead_arg("nstep_returns", L, r.size(0)), cur_stream(r)),
         "nstep_returns");
 }
 
@@ -658,6 +665,7 @@ void returns_scan(Tensor r, Tensor v, Tensor d, Tensor ret, Tensor adv, int64_t 
   check_returns(r, v, d, ret, adv);
   const int T = r.size(0), N = r.size(1);
   TORCH_CHECK(mode == 1 || mode == 2, "returns_scan: mode 1 (n-step) or 2 (GAE)");
+  const int Lw = look_ahead_arg("returns_scan", L, T);
   int E, CH, K, blocks;
   aca_returns_scan_geometry(T, N, &E, &CH, &K, &blocks);
   need(part, at::kDouble, "part");
@@ -686,7 +694,7 @@ void returns_scan(Tensor r, Tensor v, Tensor d, Tensor ret, Tensor adv, int64_t 
   a.T = T;
   a.N = N;
   a.mode = (int)mode;
-  a.L = (int)L;
+  a.L = Lw;
   a.norm = norm ? 1 : 0;
   a.gamma = (float)gamma;
   a.lam = (float)lam;
@@ -2143,7 +2151,7 @@ aca::HeadBwdArgs head_args(const char* op, bool exact, const Tensor& z, const Te
   a.dn = ptr<uint8_t>(dones);
   a.T = (int)T;
   a.N = (int)N;
-  a.L = (int)L;
+  a.L = look_ahead_arg(op, L, T);
   a.returns_mode = (int)returns_mode;
   a.norm_adv = norm_adv ? 1 : 0;
   a.gamma = (float)gamma;
@@ -2389,7 +2397,7 @@ void ac_loss(Tensor logits, int64_t ldl, c10::optional<Tensor> value, int64_t ld
   a.dn = optr<uint8_t>(dones);
   a.T = T;
   a.N = N;
-  a.L = (int)L;
+  a.L = returns_mode == 1 ? look_ahead_arg("ac_loss", L, T) : (int)L;
   a.gamma = (float)gamma;
   a.lam = (float)lam;
   a.norm_adv = norm_adv ? 1 : 0;

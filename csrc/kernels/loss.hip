@@ -1090,7 +1090,8 @@ __global__ void __launch_bounds__(AE_THREADS) a2c_head_env_kernel(A2cEnvArgs arg
 extern "C" hipError_t aca_head_bwd(const aca::HeadBwdArgs* args, int A, hipStream_t stream) {
   aca::HeadBwdArgs a = *args;
   const int N = a.N, B = a.T * N;
-  if (B < 1 || B > aca::HB_MAXB || N > 256 || A < 2 || A > 7 || (a.returns_mode != 1 && a.returns_mode != 2))
+  if (B < 1 || B > aca::HB_MAXB || N > 256 || A < 2 || A > 7 || (a.returns_mode != 1 && a.returns_mode != 2) ||
+      a.L < 1)   // L < 1: the n-step window would end before it starts (reads before the rollout)
     return hipErrorInvalidValue;
   a.B = B;
   switch (A) {
@@ -1106,7 +1107,7 @@ extern "C" hipError_t aca_a2c_head(const aca::A2cHeadArgs* args, int A, hipStrea
   aca::A2cHeadArgs a = *args;
   const int B = a.h.T * a.h.N;
   if (B < 1 || B > aca::AH_MAXB || a.h.N > aca::AH_MAXN || A < 2 || A > 7 ||
-      (a.h.returns_mode != 1 && a.h.returns_mode != 2))
+      (a.h.returns_mode != 1 && a.h.returns_mode != 2) || a.h.L < 1)
     return hipErrorInvalidValue;
   if (a.hpart && (a.S < 1 || a.S > aca::FC_MAX_PLANES || !a.bfc || !a.bh || !a.bar ||
                   reinterpret_cast<uintptr_t>(a.hpart) % 16 || reinterpret_cast<uintptr_t>(a.bfc) % 16 ||
@@ -1127,7 +1128,7 @@ extern "C" hipError_t aca_a2c_head_env(const aca::A2cEnvArgs* args, int A, hipSt
   aca::A2cEnvArgs a = *args;
   const int T = a.h.T, N = a.h.N;
   if (T < 1 || T > aca::AE_MAXT || N < 1 || A < 2 || A > 7 || (a.h.returns_mode != 1 && a.h.returns_mode != 2) ||
-      !a.pWh || !a.pbfc || !a.pbh || !a.spart)
+      !a.pWh || !a.pbfc || !a.pbh || !a.spart || a.h.L < 1)
     return hipErrorInvalidValue;
   if (a.hpart && (a.S < 1 || a.S > aca::FC_MAX_PLANES || !a.bfc || !a.bh ||
                   reinterpret_cast<uintptr_t>(a.hpart) % 16 || reinterpret_cast<uintptr_t>(a.bfc) % 16 ||
@@ -1149,6 +1150,7 @@ extern "C" hipError_t aca_ac_loss(const aca::LossArgs* args, hipStream_t stream)
   if (A > 64 || a.dbias_n > aca::CAT_MAX + 1 || (!a.gaussian && A > aca::CAT_MAX)) return hipErrorInvalidValue;
   if (a.returns_mode && (a.T * a.N != a.B || !a.rew || !a.val || !a.dn || !a.ret_w || !a.adv_w))
     return hipErrorInvalidValue;
+  if (a.returns_mode == 1 && a.L < 1) return hipErrorInvalidValue;   // the window would end before it starts
   if (!a.gaussian && A >= 2 && A <= 19) {
     switch (A) {
 #define ACA_LOSS_CASE(n) \

@@ -542,6 +542,7 @@ extern "C" hipError_t aca_gae(const float* r, const float* v, const uint8_t* d, 
 extern "C" hipError_t aca_nstep(const float* r, const float* v, const uint8_t* d, float* tgt, float* adv, int T,
                                 int N, float gamma, int L, hipStream_t stream) {
   if (T <= 0 || N <= 0) return hipSuccess;
+  if (L < 1) return hipErrorInvalidValue;   // the window [t, t + L) would end before it starts
   const int tot = T * N;
   aca::nstep_kernel<<<(tot + 255) / 256, 256, 0, stream>>>(r, v, d, tgt, adv, T, N, gamma, L);
   return hipGetLastError();
@@ -585,6 +586,7 @@ extern "C" void aca_returns_scan_geometry(int T, int N, int* E, int* CH, int* K,
 extern "C" hipError_t aca_returns_scan(const aca::RetScanArgs* args, hipStream_t stream) {
   aca::RetScanArgs a = *args;
   if (a.T <= 0 || a.N <= 0) return hipSuccess;
+  if (a.L < 1) return hipErrorInvalidValue;   // the window [t, t + L) would end before it starts
   int blocks;
   aca_returns_scan_geometry(a.T, a.N, &a.E, &a.CH, &a.K, &blocks);
   aca::returns_scan_kernel<<<blocks, aca::RS_THREADS, 0, stream>>>(a);
