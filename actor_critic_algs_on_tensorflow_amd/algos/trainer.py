@@ -136,7 +136,8 @@ class ActorCriticTrainer:
             cfg.env, cfg.num_envs, device=self.device, seed=cfg.seed, env_offset=self.rank * cfg.num_envs,
             frame_stack=fs)
         self.model = (model if model is not None else
-                      build_model(self.env, cfg.model, cfg.model_variant, seed=cfg.seed)).to(self.device)
+                      build_model(self.env, cfg.model, cfg.model_variant, seed=cfg.seed,
+                                  **cfg.mlp_kwargs())).to(self.device)
         self.flat = FlatParams(self.model.param_groups(), self.device)
         if cfg.norm_obs:
             self._check_norm_obs()
@@ -459,6 +460,15 @@ class ActorCriticTrainer:
         if self.model.actor.ac_dim > 16 or self.env.obs_dtype != torch.float32 or len(self.env.obs_shape) != 1:
             if self.cfg.engine == "native":
                 raise ValueError("the native MLP engine needs fp32 vector observations and at most 16 actions")
+            return False
+        # tower shapes outside the engine's limits (custom towers, config.check_mlp_tower): native refuses, auto falls
+        # back to the torch engine, which has none
+        from ..ops.mlp import MLPEngine
+        try:
+            MLPEngine.check_towers(self.model)
+        except ValueError:
+            if self.cfg.engine == "native":
+                raise
             return False
         _native.require()
         return True

@@ -113,13 +113,23 @@ class Agent:
         from .ops.optim import FlatParams
         from . import _native
         _native.require()
+        mlp_ok = isinstance(self.model, MLPActorCritic) and self.model.actor.ac_dim <= 16
+        if mlp_ok:
+            # towers outside the engine's limits (a width-40 tower trained on the torch engine): native refuses, auto
+            # takes the PyTorch modules -- decided before the parameters are re-homed
+            from .ops.mlp import MLPEngine
+            try:
+                MLPEngine.check_towers(self.model)
+            except ValueError:
+                if self.engine_kind == "native":
+                    raise
+                return None
         flat = FlatParams(self.model.param_groups(), self.device)   # re-homes the parameters into one slab
         if isinstance(self.model, CNNActorCritic):
             from .algos.engine import CNNEngine
             shadow = flat.data.to(torch.bfloat16)
             self._eng = ("cnn", CNNEngine(self.model, flat, shadow), flat)
-        elif isinstance(self.model, MLPActorCritic) and self.model.actor.ac_dim <= 16:
-            from .ops.mlp import MLPEngine
+        elif mlp_ok:
             self._eng = ("mlp", MLPEngine(self.model, flat), flat)
             self._eng[1].obs_norm = self.obs_norm   # the launches normalise their input tiles
         elif self.engine_kind == "native":
@@ -154,10 +164,11 @@ class Agent:
         return act, logp, ent
 
     @classmethod
-    def for_env(cls, env_id, family="auto", variant="basic", frames=1, device="cpu", seed=0):
+    def for_env(cls, env_id, family="auto", variant="basic", frames=1, device="cpu", seed=0, **towers):
+        """``towers``: ``actor_hidden`` / ``critic_hidden`` / ``hidden_act`` / ``mlp_init`` of ``build_model``."""
         from .models.policy import build_model
         env = E.make(env_id, 1, device="cpu", frame_stack=4 if ("Pong" in env_id or "Breakout" in env_id) else frames)
-        return cls(build_model(env, family, variant, seed=seed), env_id, device, seed)
+        return cls(build_model(env, family, variant, seed=seed, **towers), env_id, device, seed)
 
     @classmethod
     def from_checkpoint(cls, path, env_id, frames=1, device="cpu", variant=None):
@@ -165,10 +176,20 @@ class Agent:
         from . import ckpt
         t = ckpt.load_tensors(path)
         v = variant or ckpt.detect_variant(t.keys())
-        fam = "mlp" if v in ("a3c", "basic") else "auto"
-        agent = cls.for_env(env_id, family=fam, variant=v if v != "generic" else "basic", frames=frames,
-                            device="cpu")
-        ckpt.load_model(agent.model, t, v if v != "generic" else "basic", strict=True)
+        if v == "custom" or (variant is not None and ckpt.detect_variant(t.keys()) == "custom"):
+            # custom MLP towers: rebuilt from the architecture the bundle carries (_acamd/mlp_arch)
+            arch = ckpt.mlp_arch(t)
+            if arch is None:
+                raise KeyError(f"checkpoint {path} has custom MLP tower tensors but no {ckpt.MLP_ARCH_PREFIX}* keys")
+            agent = cls.for_env(env_id, family="mlp", variant=variant if variant in ("a3c", "basic") else "basic",
+                                frames=frames, device="cpu", **arch)
+            ckpt.check_mlp_arch(agent.model, t, path)   # (the per-tower activations the bundle records)
+            ckpt.load_model(agent.model, t, "basic", strict=True)
+        else:
+            fam = "mlp" if v in ("a3c", "basic") else "auto"
+            agent = cls.for_env(env_id, family=fam, variant=v if v != "generic" else "basic", frames=frames,
+                                device="cpu")
+            ckpt.load_model(agent.model, t, v if v != "generic" else "basic", strict=True)
         agent.model.to(device)
         agent.device = torch.device(device)
         sd = ckpt.obs_norm_state(t)

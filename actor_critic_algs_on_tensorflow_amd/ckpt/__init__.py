@@ -14,6 +14,17 @@ This module writes and reads the same files through the C++ codec (:mod:`.codec`
       written as ``<var>/Adam`` (m) and ``<var>/Adam_1`` (v) plus ``<scope>/beta{1,2}_power`` as TF's Saver does when
       it is built after the optimisers (the Basic_AC case).
   Kernels are stored ``[in, out]`` in both frameworks, so no transposes happen.
+* custom MLP towers (``TrainConfig.actor_hidden`` / ``critic_hidden`` / ``hidden_act``; the reference has no names for
+  them): ``acamd_mlp/{actor,critic}/hidden_<i>/{kernel,bias}``, ``acamd_mlp/actor/{mu_layer|logits}/...``,
+  ``acamd_mlp/actor/log_std``, ``acamd_mlp/critic/value/...``, and the architecture under ``_acamd/mlp_arch/``:
+  ``actor_hidden`` / ``critic_hidden`` (int32 vectors, the widths as built), ``custom`` (int32 [actor, critic]: whose
+  widths were given), ``hidden_act`` (int32, as given: 0 none -- the lrelu actor / relu critic --, 1 relu, 2 lrelu,
+  3 tanh; with a name both towers are custom), ``tower_acts`` (int32 [actor, critic], the activation each tower was
+  built with, checked against the rebuilt model) and ``mlp_init`` (int32: 0 reference, 1 orthogonal).
+  ``detect_variant`` calls these bundles ``"custom"``; a model of reference towers keeps the names above. When only
+  ONE tower's widths were given (and no ``hidden_act``) the other is the reference construction, and the whole model
+  is still one ``acamd_mlp`` bundle: that tower's value-path layers are ``hidden_<i>`` by position, and a layer outside
+  the value path keeps its own name (the ``basic`` critic's unused ``acamd_mlp/critic/third_layer``), so it restores.
 * any other model (the Atari CNN): ``acamd/<module path>`` names.
 * native resume state (not in the reference, which cannot resume -- SURVEY §5.4) goes under ``_acamd/...`` keys:
   optimiser moments/step/lr per group, iteration and env-step counters, env-bank state, and -- for a ``norm_obs``
@@ -85,9 +96,82 @@ def generic_tensors(model, prefix="acamd"):
     return {f"{prefix}/" + n.replace(".", "/"): p for n, p in model.named_parameters()}
 
 
+MLP_PREFIX = "acamd_mlp"
+MLP_ARCH_PREFIX = "_acamd/mlp_arch/"
+_ACT_CODE = {None: 0, "relu": 1, "lrelu": 2, "tanh": 3}
+_INIT_CODE = {"reference": 0, "orthogonal": 1}
+
+
+def custom_mlp_tensors(model):
+    """Name map of an MLP model with custom towers: hidden layers by position, everything else by its own name."""
+    t = {}
+    for scope, tower in (("actor", model.actor), ("critic", model.critic)):
+        pos = {n: i for i, n in enumerate(tower._hidden_names)}
+        for n, p in tower.named_parameters():
+            parts = n.split(".")
+            if parts[0] in pos:
+                parts[0] = f"hidden_{pos[parts[0]]}"
+            t[f"{MLP_PREFIX}/{scope}/" + "/".join(parts)] = p
+    return t
+
+
+def mlp_arch_tensors(model):
+    a = model.arch()
+    i32 = lambda v: np.asarray(v, dtype=np.int32)
+    return {MLP_ARCH_PREFIX + "actor_hidden": i32(list(model.actor.hidden)),
+            MLP_ARCH_PREFIX + "critic_hidden": i32(list(model.critic.hidden)),
+            MLP_ARCH_PREFIX + "custom": i32([int(a["actor_hidden"] is not None), int(a["critic_hidden"] is not None)]),
+            MLP_ARCH_PREFIX + "tower_acts": i32([_ACT_CODE[model.actor.activation], _ACT_CODE[model.critic.activation]]),
+            MLP_ARCH_PREFIX + "hidden_act": i32(_ACT_CODE[a["hidden_act"]]),
+            MLP_ARCH_PREFIX + "mlp_init": i32(_INIT_CODE[a["mlp_init"]])}
+
+
+def mlp_arch(tensors):
+    """The tower arguments of ``build_model`` stored in a custom-tower bundle, or None (reference towers)."""
+    if MLP_ARCH_PREFIX + "custom" not in tensors:
+        return None
+    g = lambda k: np.array(tensors[MLP_ARCH_PREFIX + k]).reshape(-1)
+    ca, cc = (int(x) for x in g("custom"))
+    act = {v: k for k, v in _ACT_CODE.items()}[int(g("hidden_act")[0])]
+    init = {v: k for k, v in _INIT_CODE.items()}[int(g("mlp_init")[0])]
+    return {"actor_hidden": tuple(int(w) for w in g("actor_hidden")) if ca else None,
+            "critic_hidden": tuple(int(w) for w in g("critic_hidden")) if cc else None,
+            "hidden_act": act, "mlp_init": init}
+
+
+def check_mlp_arch(model, tensors, path=""):
+    """Resume: the bundle's towers must be the model's. A mismatch is a ``ValueError`` that names both."""
+    from ..models.policy import MLPActorCritic
+    if not isinstance(model, MLPActorCritic):
+        return
+    stored = mlp_arch(tensors)
+    if stored is None and not model.custom_towers:
+        return
+    have = model.arch()
+    ref = {"actor_hidden": None, "critic_hidden": None, "hidden_act": None}
+    stored = stored or ref
+    for k in ("actor_hidden", "critic_hidden", "hidden_act"):
+        if stored[k] != have[k]:
+            raise ValueError(f"checkpoint {path} was written with {k}={stored[k]!r} (actor_hidden="
+                             f"{stored['actor_hidden']!r}, critic_hidden={stored['critic_hidden']!r}, hidden_act="
+                             f"{stored['hidden_act']!r}; None = the reference's), the config asks for {k}={have[k]!r} "
+                             f"(actor_hidden={have['actor_hidden']!r}, critic_hidden={have['critic_hidden']!r}, "
+                             f"hidden_act={have['hidden_act']!r})")
+    if MLP_ARCH_PREFIX + "tower_acts" in tensors:
+        acts = [int(x) for x in np.array(tensors[MLP_ARCH_PREFIX + "tower_acts"]).reshape(-1)]
+        mine = [_ACT_CODE[model.actor.activation], _ACT_CODE[model.critic.activation]]
+        if acts != mine:
+            names = {v: k for k, v in _ACT_CODE.items()}
+            raise ValueError(f"checkpoint {path} was written with hidden_act={stored['hidden_act']!r} (actor "
+                             f"{names[acts[0]]}, critic {names[acts[1]]}); this model has hidden_act="
+                             f"{have['hidden_act']!r} (actor {names[mine[0]]}, critic {names[mine[1]]})")
+
+
 def model_tensors(model, variant="basic", opts=None):
     """Name map for a model built by :func:`..models.policy.build_model`."""
     from ..models.policy import MLPActorCritic
+    if isinstance(model, MLPActorCritic) and model.custom_towers:
+        return custom_mlp_tensors(model)
     if isinstance(model, MLPActorCritic):
         lr = {}
         if opts:
@@ -259,6 +343,8 @@ def save_trainer(trainer, path=None):
         os.makedirs(cfg.checkpoint_dir, exist_ok=True)
         path = os.path.join(cfg.checkpoint_dir, f"{base}-{trainer.iteration}")
     tensors = dict(model_tensors(trainer.model, cfg.model_variant, trainer.opts))
+    if getattr(trainer.model, "custom_towers", False):
+        tensors.update(mlp_arch_tensors(trainer.model))
     for g, opt in trainer.opts.items():
         for k, v in opt.state_dict().items():
             if k in _SLAB_STATE:   # per parameter name: independent of the slab layout (parameter order, padding)
@@ -343,6 +429,7 @@ def load_model(model, tensors, variant="basic", strict=True):
 
 def load_trainer(trainer, path):
     t = load_tensors(path)
+    check_mlp_arch(trainer.model, t, path)
     load_model(trainer.model, t, trainer.cfg.model_variant)
     # the model parameters are views into the flat slab; refresh the bf16 shadow of the native engine
     if trainer.shadow is not None:
@@ -399,6 +486,8 @@ def load_trainer(trainer, path):
 
 def detect_variant(names):
     names = list(names)
+    if any(n.startswith(MLP_PREFIX + "/") for n in names):
+        return "custom"
     if any(n.startswith("global_actor/") for n in names):
         return "a3c"
     if any(n.startswith("Actor/") for n in names):
@@ -408,4 +497,4 @@ def detect_variant(names):
 
 __all__ = ["codec", "save_trainer", "load_trainer", "save_tensors", "load_tensors", "load_model",
            "reference_tensors", "model_tensors", "latest_checkpoint", "detect_variant", "obs_norm_state",
-           "reward_norm_state"]
+           "reward_norm_state", "custom_mlp_tensors", "mlp_arch_tensors", "mlp_arch", "check_mlp_arch"]

@@ -50,12 +50,26 @@ def build_parser():
     p.add_argument("--stop-return", default=None, type=float,
                    help="stop once the episode window is full and its mean return reaches this "
                         "(TrainConfig.stop_return; needs --ep-window, one device)")
+    p.add_argument("--actor-hidden", default=None, type=_widths,
+                   help="hidden widths of the actor, e.g. 64,64 (TrainConfig.actor_hidden; --algo a2c|ppo, MLP models)")
+    p.add_argument("--critic-hidden", default=None, type=_widths,
+                   help="hidden widths of the critic, e.g. 64,64 (TrainConfig.critic_hidden)")
+    p.add_argument("--hidden-act", default=None, choices=["tanh", "relu", "lrelu"],
+                   help="activation of the hidden layers of both towers (TrainConfig.hidden_act)")
+    p.add_argument("--mlp-init", default=None, choices=["reference", "orthogonal"],
+                   help="initialisers of the MLP towers (TrainConfig.mlp_init)")
     return p
 
 
-def main(argv=None):
-    a = build_parser().parse_args(argv)
-    from ..api import train
+def _widths(text):
+    """``"64,64"`` -> ``(64, 64)``."""
+    try:
+        return tuple(int(w) for w in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected comma-separated widths such as 64,64, got {text!r}") from None
+
+
+def config_from_args(a):
     from ..config import preset
     name = a.preset or ("basic_ac" if a.algo == "basic_ac" else ("breakout_ppo" if a.algo == "ppo" else "cartpole_cpu"))
     kw = dict(env=a.env, seed=a.seed, save_every=a.save_every, outdir=a.outdir, checkpoint_dir=a.checkpoint_dir,
@@ -79,7 +93,16 @@ def main(argv=None):
         kw["ep_window"] = a.ep_window
     if a.stop_return is not None:
         kw["stop_return"] = a.stop_return
-    cfg = preset(name, **kw)
+    for k in ("actor_hidden", "critic_hidden", "hidden_act", "mlp_init"):
+        if getattr(a, k) is not None:
+            kw[k] = getattr(a, k)
+    return preset(name, **kw)
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    from ..api import train
+    cfg = config_from_args(a)
     res = train(cfg)
     print("done: %d iterations, %d env steps, %.1f env-steps/s" % (res.iterations, res.env_steps,
                                                                     res.env_steps_per_sec))

@@ -65,7 +65,61 @@ CHOICES = {
     "grad_bucket_dtype": {"fp32", "bf16"},
     "dp_capture": {"auto", "segments"},
     "mode": {"train", "debug", "debug-light", "debug-full"},
+    "hidden_act": {None, "tanh", "relu", "lrelu"},   # None: the reference's lrelu actor / relu critic
+    "mlp_init": {"reference", "orthogonal"},
 }
+
+# Limits of the native MLP engine's tower shapes (csrc/kernels/mlp.hip; ops/mlp.py). The torch engine has none.
+MLP_MAX_HIDDEN = 4        # MLP_MAXL = 5 layers of a tower descriptor, the head included
+MLP_MAX_WIDTH = 256       # MLP_MAXW: one layer's activations are one LDS tile of at most 16 column tiles
+MLP_PARTS = 256           # sum-of-squares slots of a tower (global-norm clip), one per 16 x 16 tile of every dW
+MLP_MAX_LDS = 140 * 1024  # dynamic LDS the generic kernel's launcher grants
+
+
+def _ngp2(w):
+    g = (w + 15) // 16
+    return 1 if g <= 1 else 2 if g <= 2 else 4 if g <= 4 else 8 if g <= 8 else 16
+
+
+def mlp_tower_slots(widths):
+    """Sum-of-squares slots of a tower ``[D, h_0, ..., out]``: one per 16 x 16 tile of every weight gradient."""
+    return sum(((k + 15) // 16) * ((n + 15) // 16) for k, n in zip(widths[:-1], widths[1:]))
+
+
+def mlp_tower_lds_bytes(widths):
+    """Dynamic LDS of the generic kernel's train launch for a tower ``[D, h_0, ..., out]`` (``MLPEngine.lds_bytes``):
+    the input tile, every layer's output tile, and the two data-gradient tiles."""
+    return 4 * (sum(16 * (16 * _ngp2(w) + 4) for w in widths) + 2 * 16 * (MLP_MAX_WIDTH + 4))
+
+
+def check_mlp_tower(field, hidden, in_dim=None, out_dim=None, extra_slots=0):
+    """The native MLP engine's limits on one tower's hidden widths, as ``ValueError``s that name ``field`` and the
+    limit. ``in_dim`` / ``out_dim`` (known once the env is: observation width, head width) add the checks that need
+    the whole tower; ``extra_slots``: 1 for a continuous actor (its ``log_std`` takes one slot)."""
+    hidden = tuple(int(w) for w in hidden)
+    if not 1 <= len(hidden) <= MLP_MAX_HIDDEN:
+        raise ValueError(f"{field}={hidden!r}: a tower has 1 to {MLP_MAX_HIDDEN} hidden layers (the engine's tower "
+                         f"descriptor holds MLP_MAXL = {MLP_MAX_HIDDEN + 1} layers, the head included)")
+    for w in hidden:
+        if not 1 <= w <= MLP_MAX_WIDTH:
+            raise ValueError(f"{field}={hidden!r}: width {w} is outside 1..{MLP_MAX_WIDTH} (MLP_MAXW)")
+        if w > 32 and w % 16:
+            raise ValueError(f"{field}={hidden!r}: width {w} is above 32 and not a multiple of 16 (the data-gradient "
+                             "weight loads are 16-wide vectors)")
+    # (before the env is known: the narrowest input and head there can be, a lower bound of what the tower needs)
+    widths = [int(in_dim) if in_dim is not None else 1] + list(hidden) + [int(out_dim) if out_dim is not None else 1]
+    if in_dim is not None and not 1 <= int(in_dim) <= MLP_MAX_WIDTH:
+        raise ValueError(f"{field}: observation width {in_dim} is outside 1..{MLP_MAX_WIDTH} (MLP_MAXW)")
+    slots = mlp_tower_slots(widths) + extra_slots
+    if slots > MLP_PARTS:
+        raise ValueError(f"{field}={hidden!r}: the tower's weight gradients are {slots} 16 x 16 tiles"
+                         f"{' (+1 for log_std)' if extra_slots else ''}, and a tower has MLP_PARTS = {MLP_PARTS} "
+                         "sum-of-squares slots, one per tile (sum of ceil(K/16) * ceil(N/16) over its layers; a "
+                         "256 -> 256 layer alone needs 256)")
+    if mlp_tower_lds_bytes(widths) > MLP_MAX_LDS:
+        raise ValueError(f"{field}={hidden!r}: the tower's activation tiles need {mlp_tower_lds_bytes(widths)} bytes of "
+                         f"LDS, above the {MLP_MAX_LDS} the kernel's launcher grants")
+    return hidden
 
 
 @dataclass
@@ -158,6 +212,17 @@ class TrainConfig:
     cuda_graph: bool = True
     reuse_rollout_acts: bool = True   # native A2C: the rollout's activations are the learner's forward (exact)
     fused_rollout: bool = True        # native MLP engine + MuJoCo-shaped bank: the whole rollout in one launch
+    # -- MLP towers (models/mlp.py) --------------------------------------------------------------------------------
+    # hidden widths of the actor / critic (None: the reference's 128-128-64 / 256-128(-128, variant a3c)); the hidden
+    # activation of both (None: the reference's lrelu actor / relu critic); the initialisers. A tower is "custom" when
+    # its *_hidden or hidden_act is given: 1..4 hidden layers, widths 1..256 (above 32: multiples of 16), at most 256
+    # 16 x 16 weight-gradient tiles per tower -- the native MLP engine's limits (check_mlp_tower), checked here for
+    # engine "native" / "auto"; engine="torch" has none. a2c / ppo on the MLP models only. Custom towers run the
+    # generic kernels (per-step rollout); the one-launch rollout and the SPEC train path stay the reference's
+    actor_hidden: tuple | None = None
+    critic_hidden: tuple | None = None
+    hidden_act: str | None = None     # tanh | relu | lrelu
+    mlp_init: str = "reference"       # reference | orthogonal (gain sqrt 2 hidden, 0.01 policy head, 1 value head)
     engine_opts: EngineOpts = field(default_factory=EngineOpts)   # kernel selection of the native CNN engine
     total_updates: int = 1000
     # -- distributed -----------------------------------------------------------------------------------------------
@@ -195,7 +260,7 @@ class TrainConfig:
         for name, allowed in CHOICES.items():
             v = getattr(self, name)
             if v not in allowed:
-                raise ValueError(f"TrainConfig.{name}={v!r}: expected one of {sorted(allowed)}")
+                raise ValueError(f"TrainConfig.{name}={v!r}: expected one of {sorted(allowed, key=str)}")
         if self.lr_schedule == "linear" and self.kl_adaptive_lr:
             raise ValueError("lr_schedule='linear' with kl_adaptive_lr=True: the KL controller owns the actor lr, so "
                              "only the critic would decay; pick one")
@@ -254,8 +319,42 @@ class TrainConfig:
             if not self.stdout_freq:
                 raise ValueError("TrainConfig.stop_return needs stdout_freq > 0: the window is read where a log row is "
                                  "produced")
+        for name in ("actor_hidden", "critic_hidden"):
+            v = getattr(self, name)
+            if v is None:
+                continue
+            if isinstance(v, (str, bytes)) or not hasattr(v, "__iter__"):
+                raise ValueError(f"TrainConfig.{name}={v!r}: expected a sequence of hidden widths, e.g. (64, 64)")
+            try:
+                v = tuple(int(w) for w in v)
+            except (TypeError, ValueError):
+                raise ValueError(f"TrainConfig.{name}={getattr(self, name)!r}: hidden widths are integers") from None
+            if not v or any(w < 1 for w in v):
+                raise ValueError(f"TrainConfig.{name}={v!r}: needs at least one hidden layer, every width >= 1")
+            if self.engine != "torch":
+                check_mlp_tower(f"TrainConfig.{name}", v)
+            setattr(self, name, v)
+        if self.custom_mlp:
+            if self.algo not in ("a2c", "ppo"):
+                raise ValueError(f"TrainConfig.actor_hidden / critic_hidden / hidden_act / mlp_init with "
+                                 f"algo={self.algo!r}: the reference-parity trainers keep the reference networks; use "
+                                 "a2c or ppo")
+            if self.model == "cnn":
+                raise ValueError("TrainConfig.actor_hidden / critic_hidden / hidden_act / mlp_init with model='cnn': "
+                                 "they configure the MLP towers; the CNN model has none")
         if self.look_ahead is not None and int(self.look_ahead) < 1:
             raise ValueError(f"TrainConfig.look_ahead={self.look_ahead}: must be >= 1 (None = the whole rollout)")
+
+    @property
+    def custom_mlp(self):
+        """Any MLP tower field away from "the reference towers"."""
+        return (self.actor_hidden is not None or self.critic_hidden is not None or self.hidden_act is not None
+                or self.mlp_init != "reference")
+
+    def mlp_kwargs(self):
+        """The tower arguments of ``models.policy.build_model``."""
+        return dict(actor_hidden=self.actor_hidden, critic_hidden=self.critic_hidden, hidden_act=self.hidden_act,
+                    mlp_init=self.mlp_init)
 
     def replace(self, **kw):
         return dataclasses.replace(self, **kw)
@@ -313,6 +412,10 @@ PRESETS = {
                            critic_lr=1e-3, ppo_epochs=10, ppo_minibatches=32, ppo_clip=0.2, ent_coef=0.0,
                            vf_coef=0.5, max_grad_norm=0.5, device="cuda", dtype="fp32"),
 }
+# the usual continuous-control networks on the same task: two tanh layers of 64 per tower, orthogonal init (custom
+# towers: per-step rollout on the generic kernels, no one-launch rollout)
+PRESETS["halfcheetah_ppo_tanh64"] = dict(PRESETS["mujoco_ppo_dp8"], actor_hidden=(64, 64), critic_hidden=(64, 64),
+                                         hidden_act="tanh", mlp_init="orthogonal")
 
 
 def preset(name, **overrides) -> TrainConfig:

@@ -70,13 +70,33 @@ class ActorCritic(nn.Module):
 
 
 class MLPActorCritic(ActorCritic):
-    def __init__(self, ob_dim, ac_dim, discrete, ac_scale=None, variant="basic", generator=None):
+    def __init__(self, ob_dim, ac_dim, discrete, ac_scale=None, variant="basic", generator=None, actor_hidden=None,
+                 critic_hidden=None, hidden_act=None, mlp_init="reference"):
+        """``actor_hidden`` / ``critic_hidden`` (hidden widths), ``hidden_act`` (``tanh | relu | lrelu`` on the hidden
+        layers of both towers) and ``mlp_init`` select custom towers (``models/mlp.py``); the defaults build the
+        reference's, with the same RNG draws and parameter names as ever."""
         super().__init__()
         self.discrete = discrete
+        # the tower arguments as given (arch()): None keeps the reference's widths / its lrelu actor and relu critic
+        self.actor_hidden = None if actor_hidden is None else tuple(int(w) for w in actor_hidden)
+        self.critic_hidden = None if critic_hidden is None else tuple(int(w) for w in critic_hidden)
+        self.hidden_act = hidden_act
         # the reference builds the critic first (Basic_AC/run_AC.py:197-198)
-        self.critic = MLPCritic(ob_dim, variant=variant, generator=generator)
+        self.critic = MLPCritic(ob_dim, variant=variant, generator=generator, hidden=critic_hidden,
+                                activation=hidden_act, init=mlp_init)
         self.actor = MLPActor(ob_dim, ac_dim, discrete, ac_scale if ac_scale is not None else 1.0, variant,
-                              generator=generator)
+                              generator=generator, hidden=actor_hidden, activation=hidden_act, init=mlp_init)
+
+    @property
+    def custom_towers(self):
+        return self.actor.custom or self.critic.custom
+
+    def arch(self):
+        """The tower arguments this model was built with -- what a checkpoint needs to rebuild it (``ckpt`` stores
+        them under ``_acamd/mlp_arch``), each as given: ``hidden_act=None`` (the lrelu actor / relu critic) is not the
+        same architecture as either name, and a tower whose widths were not given has the reference's."""
+        return {"actor_hidden": self.actor_hidden, "critic_hidden": self.critic_hidden,
+                "hidden_act": self.hidden_act, "mlp_init": self.actor.init}
 
     def pi_params(self, obs):
         return self.actor(obs)
@@ -118,17 +138,23 @@ class CNNActorCritic(ActorCritic):
         return {"shared": [p for p in self.parameters() if p is not fck] + [fck]}
 
 
-def build_model(env, family="auto", variant="basic", seed=0, hidden=512):
-    """Builds the model family for an env bank (``family``: auto | mlp | cnn)."""
+def build_model(env, family="auto", variant="basic", seed=0, hidden=512, actor_hidden=None, critic_hidden=None,
+                hidden_act=None, mlp_init="reference"):
+    """Builds the model family for an env bank (``family``: auto | mlp | cnn). ``actor_hidden`` / ``critic_hidden`` /
+    ``hidden_act`` / ``mlp_init``: the MLP family's towers (``TrainConfig`` fields of the same names)."""
+    tw = dict(actor_hidden=actor_hidden, critic_hidden=critic_hidden, hidden_act=hidden_act, mlp_init=mlp_init)
     g = torch.Generator().manual_seed(int(seed))
     obs_shape = env.obs_shape
     if family == "auto":
         family = "cnn" if len(obs_shape) == 3 else "mlp"
     if family == "cnn":
+        if actor_hidden is not None or critic_hidden is not None or hidden_act is not None or mlp_init != "reference":
+            raise ValueError("build_model: actor_hidden / critic_hidden / hidden_act / mlp_init configure the MLP "
+                             "towers; the cnn family has none")
         return CNNActorCritic(env.action_space.n, in_ch=obs_shape[0], hidden=hidden, generator=g)
     if env.is_discrete:
-        return MLPActorCritic(obs_shape[0], env.action_space.n, True, None, variant, generator=g)
+        return MLPActorCritic(obs_shape[0], env.action_space.n, True, None, variant, generator=g, **tw)
     import numpy as np
     sp = env.action_space
     ac_scale = np.maximum(sp.high, np.abs(sp.low))
-    return MLPActorCritic(obs_shape[0], sp.shape[0], False, ac_scale, variant, generator=g)
+    return MLPActorCritic(obs_shape[0], sp.shape[0], False, ac_scale, variant, generator=g, **tw)

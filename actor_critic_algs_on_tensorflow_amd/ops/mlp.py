@@ -106,7 +106,8 @@ class TimeoutBootWorkspace:
 class MLPEngine:
     def __init__(self, model, flat):
         from ..models.policy import MLPActorCritic
-        assert isinstance(model, MLPActorCritic)
+        if not isinstance(model, MLPActorCritic):
+            raise ValueError(f"MLPEngine needs an MLPActorCritic, got {type(model).__name__}")
         self.model = model
         self.flat = flat
         self.dev = flat.data.device
@@ -117,20 +118,8 @@ class MLPEngine:
         self.head = 1 if self.discrete else 2
         if self.A > 16:
             raise ValueError("MLP engine heads support at most 16 actions")
-        out_layer = actor.logits if self.discrete else actor.mu_layer
-        self.towers = [
-            [actor.first_layer, actor.second_layer, actor.third_layer, out_layer],
-            [critic.first_layer, critic.second_layer] + ([critic.third_layer] if critic.variant == "a3c" else [])
-            + [critic.value],
-        ]
-        for tw in self.towers:
-            assert len(tw) <= MAXL and tw[0].in_features == self.D
-            for i, lay in enumerate(tw):
-                assert lay.in_features <= MAXW and lay.out_features <= MAXW
-                # layer widths above 32 must be multiples of 16 (vectorised data-gradient weight loads, mlp.hip)
-                assert lay.out_features <= 32 or lay.out_features % 16 == 0
-                if i:
-                    assert lay.in_features == tw[i - 1].out_features
+        self.towers = self.check_towers(model)
+        self.hidden_tanh = [any(l.activation == "tanh" for l in tw[:-1]) for tw in self.towers]
         idx = {id(p): i for i, p in enumerate(flat.params)}
 
         def views(p):
@@ -163,13 +152,39 @@ class MLPEngine:
                 if i:
                     self.G[id(lay)] = torch.zeros(n, dtype=torch.float32, device=self.dev)
         self.n_weights = sum(l.in_features * l.out_features for tw in self.towers for l in tw)
-        # reference tower shapes: the train launches take the SPEC path (every weight fragment preloaded, mlp.hip)
-        self.spec = True
+        # reference tower widths: the train launches take the SPEC path (every weight fragment preloaded, mlp.hip). Its
+        # activations are the slope form (relu / lrelu, read from the descriptor at run time): no hidden tanh
+        self.spec = ([l.out_features for l in self.towers[0][:-1]] == [128, 128, 64]
+                     and [l.out_features for l in self.towers[1][:-1]] == [256, 128] and self.D <= 64
+                     and not any(self.hidden_tanh))
         # optional running observation normaliser (ops/obs_norm.py ObsNormalizer): when attached, policy_step, value,
         # evaluate and rollout_linear take RAW observations and normalise them as their input tiles are written;
         # train reads whatever it is given (the trainer feeds it the pre-normalised plane)
         self.obs_norm = None
         self.sync_shadow()
+
+    @staticmethod
+    def check_towers(model):
+        """The two towers' layers in forward order, [actor, critic], after the engine's limits: every violation is a
+        ``ValueError`` that names the tower and the limit (``config.check_mlp_tower``)."""
+        actor, critic = model.actor, model.critic
+        D, discrete = actor.ob_dim, model.discrete
+        # the layers each forward reads, in order (models/mlp.py: reference or custom towers alike)
+        towers = [list(actor.hidden_layers) + [actor.out_layer], list(critic.hidden_layers) + [critic.out_layer]]
+        from ..config import check_mlp_tower
+        for name, tw in zip(("actor_hidden", "critic_hidden"), towers):
+            if tw[0].in_features != D or any(b.in_features != a.out_features for a, b in zip(tw, tw[1:])):
+                raise ValueError(f"MLPEngine: the {name[:-7]} tower's layers do not chain from the observation width "
+                                 f"{D}: {[(l.in_features, l.out_features) for l in tw]}")
+            for lay in tw[:-1]:
+                if lay.activation not in ("tanh", "relu", "lrelu"):
+                    raise ValueError(f"MLPEngine: hidden_act={lay.activation!r} on the {name[:-7]} tower: the kernels "
+                                     "have tanh, relu and lrelu")
+            # 1..4 hidden layers, widths 1..256 (above 32: multiples of 16 -- vectorised data-gradient weight loads,
+            # mlp.hip), the sum-of-squares slots and the LDS of the generic kernel
+            check_mlp_tower(f"MLPEngine: {name}", [l.out_features for l in tw[:-1]], D, tw[-1].out_features,
+                            extra_slots=int(name == "actor_hidden" and not discrete))
+        return towers
 
     def frag_copies(self):
         """Per tower (= optimiser group actor, critic): (W view, K, N, F, G or None) -- the fragment copies the
@@ -212,6 +227,12 @@ class MLPEngine:
                     ws += [xs, dp]
                     words[base + 2 + 7 * MAXL + l] = xs.data_ptr()
                     words[base + 2 + 8 * MAXL + l] = dp.data_ptr()
+        # the launches' hidden_tanh flag (the launcher's choice of instantiation) must say what these very words say:
+        # the descriptor lives on the device, where the launcher cannot read it back
+        said = any(int(words[t * TOWER_WORDS + 2 + 2 * MAXL + l]) == ACT_CODES["tanh"]
+                   for t, tw in enumerate(self.towers) for l in range(len(tw) - 1))
+        if said != any(self.hidden_tanh):
+            raise ValueError("MLPEngine: the descriptor's hidden activations and hidden_tanh disagree")
         d = (words.to(self.dev), ws)
         self._descs[B] = d
         self._hdescs[B] = words   # CPU copy: the SPEC train path takes the tower descriptors as kernel arguments
@@ -250,7 +271,8 @@ class MLPEngine:
                     act_in, logp_old, adv, ret, v_old, ent_coef, kl_coef, float(vf_coef), float(ppo_clip),
                     float(v_clip or 0.0), bool(ppo), self.g_log_std if mode == 2 else None,
                     self.mstats if mode == 2 else None, self._mpart(B) if mode == 2 else None, stamps,
-                    self._hdescs[desc_B] if (mode == 2 and self.spec) else None, tables, nclip, go, bool(greedy))
+                    self._hdescs[desc_B] if (mode == 2 and self.spec) else None, tables, nclip, go, bool(greedy),
+                    any(self.hidden_tanh))
 
     # ------------------------------------------------------------------------------------------- API
     def policy_step(self, obs, act_out, logp_out, ent_out, v_out, tg, env_ids, key_shift, seed, greedy=False):
@@ -351,7 +373,8 @@ class MLPEngine:
         from ..envs.mujoco import MujocoShapeVecEnv
         return (isinstance(env, MujocoShapeVecEnv) and not self.discrete and self.A == LIN_ACT
                 and self.D == LIN_OBS * env.frame_stack and env.frame_stack <= 3 and self.rollout_weights_in_lds()
-                and [l.out_features for l in self.towers[0]] == [128, 128, 64, LIN_ACT])   # mlp_rollout_kernel shapes
+                and [l.out_features for l in self.towers[0]] == [128, 128, 64, LIN_ACT]   # mlp_rollout_kernel shapes
+                and [l.activation for l in self.towers[0][:-1]] == ["lrelu"] * 3)   # ... and the reference activations
 
     ROLLOUT_MAX_LDS = 150 * 1024
     ROLLOUT_NORM_LDS = 2 * 1024   # static LDS of the NORM instantiations (tables + normalised tile; mlp.hip)
@@ -397,7 +420,7 @@ class MLPEngine:
                                       env.state, env.t, env.tg, env.ep_ret, env.ep_stats, env.env_ids, env.A, env.B,
                                       env.seed, env.max_episode_steps, env.frame_stack, wlds, stamps,
                                       None if boot is None else boot.final_obs,
-                                      None if boot is None else boot.final_step, tables, nclip)
+                                      None if boot is None else boot.final_step, tables, nclip, self.hidden_tanh[0])
         if after_rollout is not None:
             after_rollout()
         self.value(st.obs.view((T + 1) * N, -1), st.values.view(-1))
@@ -419,4 +442,5 @@ class MLPEngine:
         _native.require().mlp_rollout_eval(desc, self.rollout_lds_bytes(wlds), obs0, int(steps), self.log_std,
                                            self.ac_scale, env.state, env.t, env.tg, env.ep_ret, env.env_ids, env.A,
                                            env.B, env.seed, env.max_episode_steps, env.frame_stack, wlds,
-                                           rec.ep_ret, rec.ep_len, rec.cnt, tables, nclip)
+                                           rec.ep_ret, rec.ep_len, rec.cnt, tables, nclip, None, None,
+                                           self.hidden_tanh[0])

@@ -316,7 +316,9 @@ class FusedGroupStep:
     def item_table(o, copies):
         """Item records (``optim.hip`` opt_items, 8 int64 each) covering optimiser ``o``'s whole segment: every weight
         with N % 64 == 0 as 16-row x 64-column blocks (type 1: the update plus whole 1 KB F / G fragment stores),
-        other copied weights whole (type 2, K * N <= 1024), the rest as element ranges of <= 1024 (type 0)."""
+        other copied weights whole (type 2, K * N <= 1024) or, when larger (custom tower widths), as element ranges of
+        <= 1024 of the weight (type 2 with the range's first element and the full K), the rest as element ranges of
+        <= 1024 (type 0)."""
         from .mlp import ngp2
         n = o.p.numel()
         recs, covered = [], []
@@ -332,9 +334,12 @@ class FusedGroupStep:
                         fp = F.data_ptr() + 4 * ((4 * cg) * gk + kt) * 256
                         gp = G.data_ptr() + 4 * (kt * gn + 4 * cg) * 256 if G is not None else 0
                         recs.append([1, off + kt * 16 * N + cg * 64, min(16, K - kt * 16), N, fp, gp, gk * 256, 0])
-            else:
-                assert K * N <= 1024, "small copied weights are one workgroup item"
+            elif K * N <= 1024:
                 recs.append([2, off, K, N, F.data_ptr(), G.data_ptr() if G is not None else 0, 0, 0])
+            else:
+                for o0 in range(0, K * N, 1024):
+                    recs.append([2, off + o0, min(1024, K * N - o0), N, F.data_ptr(),
+                                 G.data_ptr() if G is not None else 0, o0, K])
             covered.append((off, off + K * N))
         pos = 0
         for a, b in sorted(covered) + [(n, n)]:

@@ -1074,7 +1074,7 @@ void mlp_fwd(Tensor desc, int64_t tw_base, int64_t ntw, int64_t mode, int64_t ld
              double vf_coef, double ppo_clip, double v_clip, bool ppo, c10::optional<Tensor> g_log_std,
              c10::optional<Tensor> mstats, c10::optional<Tensor> mpart, c10::optional<Tensor> stamps,
              c10::optional<Tensor> hdesc, c10::optional<Tensor> norm_tables, double norm_clip,
-             c10::optional<Tensor> go, bool greedy) {
+             c10::optional<Tensor> go, bool greedy, bool hidden_tanh) {
   need(desc, at::kLong, "desc");
   TORCH_CHECK(desc.numel() * 8 >= (int64_t)(2 * sizeof(aca::MlpTower)), "mlp_fwd: desc too small");
   TORCH_CHECK(obs.is_cuda() && obs.scalar_type() == at::kFloat && obs.dim() == 2 && obs.stride(1) == 1,
@@ -1146,7 +1146,12 @@ void mlp_fwd(Tensor desc, int64_t tw_base, int64_t ntw, int64_t mode, int64_t ld
     const bool ok = g0 && P.nl == 4 && P.in[0] == D && P.out[0] == 128 && P.out[1] == 128 && P.out[2] == 64 &&
                     P.out[3] >= 1 && P.out[3] <= 16 && P.out[3] == A && C.nl == 3 && C.in[0] == D &&
                     C.out[0] == 256 && C.out[1] == 128 && C.out[2] == 1;
-    if (ok) {
+    // ... and no hidden tanh layer (act code 3 below a tower's top): the SPEC path has the slope activations only
+    bool desc_tanh = false;
+    for (int t = 0; t < 2; ++t)
+      for (int l = 0; l + 1 < (int)a.htw[t].nl && l + 1 < aca::MLP_MAXL; ++l) desc_tanh |= a.htw[t].act[l] == 3;
+    TORCH_CHECK(!desc_tanh || hidden_tanh, "mlp_fwd: hdesc has a hidden tanh layer but hidden_tanh is not set");
+    if (ok && !desc_tanh) {
       for (int t = 0; t < 2; ++t)
         for (int l = 0; l < (int)a.htw[t].nl; ++l)
           TORCH_CHECK(a.htw[t].F[l] && (l == 0 || a.htw[t].G[l]) && a.htw[t].xs[l] && a.htw[t].dp[l],
@@ -1183,6 +1188,8 @@ void mlp_fwd(Tensor desc, int64_t tw_base, int64_t ntw, int64_t mode, int64_t ld
   // deterministic actions (mean / first arg-max): rollout launches only
   TORCH_CHECK(!greedy || mode == 0, "mlp_fwd: greedy is a flag of rollout launches (mode 0)");
   a.greedy = greedy ? 1 : 0;
+  // towers with a hidden tanh layer (the descriptor is device-resident: its owner says so) run the TANH instantiations
+  a.hidden_tanh = hidden_tanh ? 1 : 0;
   check(aca_mlp_fwd(&a, (int)ntw, (size_t)lds, spec, cur_stream(obs)), "mlp_fwd");
 }
 
@@ -1301,7 +1308,7 @@ void mlp_rollout(Tensor desc, int64_t lds, Tensor obs, Tensor act, Tensor logp, 
                  Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, Tensor lin_A,
                  Tensor lin_B, int64_t env_seed, int64_t max_steps, int64_t k, bool wlds,
                  c10::optional<Tensor> stamps, c10::optional<Tensor> final_obs, c10::optional<Tensor> final_step,
-                 c10::optional<Tensor> norm_tables, double norm_clip) {
+                 c10::optional<Tensor> norm_tables, double norm_clip, bool hidden_tanh) {
   need(desc, at::kLong, "desc");
   TORCH_CHECK(desc.numel() * 8 >= (int64_t)sizeof(aca::MlpTower), "mlp_rollout: desc too small");
   need(obs, at::kFloat, "obs");
@@ -1377,6 +1384,8 @@ void mlp_rollout(Tensor desc, int64_t lds, Tensor obs, Tensor act, Tensor logp, 
     a.norm_istd = a.norm_mean + D;
     a.norm_clip = (float)norm_clip;
   }
+  // the descriptor is device-resident: its owner says whether a hidden layer is tanh (the launcher refuses it)
+  a.hidden_tanh = hidden_tanh ? 1 : 0;
   check(aca_mlp_rollout(&a, (size_t)lds, cur_stream(obs)), "mlp_rollout");
 }
 
@@ -1389,7 +1398,7 @@ void mlp_rollout_eval(Tensor desc, int64_t lds, Tensor obs0, int64_t steps, Tens
                       int64_t env_seed, int64_t max_steps, int64_t k, bool wlds, c10::optional<Tensor> rec_ret,
                       c10::optional<Tensor> rec_len, c10::optional<Tensor> rec_cnt,
                       c10::optional<Tensor> norm_tables, double norm_clip, c10::optional<Tensor> final_obs,
-                      c10::optional<Tensor> final_step) {
+                      c10::optional<Tensor> final_step, bool hidden_tanh) {
   need(desc, at::kLong, "desc");
   TORCH_CHECK(desc.numel() * 8 >= (int64_t)sizeof(aca::MlpTower), "mlp_rollout_eval: desc too small");
   need(obs0, at::kFloat, "obs0");
@@ -1464,6 +1473,7 @@ void mlp_rollout_eval(Tensor desc, int64_t lds, Tensor obs0, int64_t steps, Tens
     a.norm_istd = a.norm_mean + D;
     a.norm_clip = (float)norm_clip;
   }
+  a.hidden_tanh = hidden_tanh ? 1 : 0;
   check(aca_mlp_rollout(&a, (size_t)lds, cur_stream(obs0)), "mlp_rollout_eval");
 }
 
@@ -2503,7 +2513,8 @@ TORCH_LIBRARY(acamd, m) {
         "Tensor? act_out, Tensor? logp_out, Tensor? ent_out, Tensor? v_out, Tensor? act_in, Tensor? logp_old, "
         "Tensor? adv, Tensor? ret, Tensor? v_old, Tensor? ent_coef, Tensor? kl_coef, float vf_coef, float ppo_clip, "
         "float v_clip, bool ppo, Tensor? g_log_std, Tensor? mstats, Tensor? mpart=None, Tensor? stamps=None, Tensor? hdesc=None, "
-        "Tensor? norm_tables=None, float norm_clip=0.0, Tensor? go=None, bool greedy=False) -> ()");
+        "Tensor? norm_tables=None, float norm_clip=0.0, Tensor? go=None, bool greedy=False, "
+        "bool hidden_tanh=False) -> ()");
   m.def("mlp_wgrad(Tensor items, int nrt, int nsplit, Tensor? g_log_std, int A, Tensor? ls_part, float ls_clip, "
         "Tensor? stats, Tensor ent_coef, Tensor kl_coef, Tensor mpart, int mpart_rows, Tensor? bump, "
         "Tensor? kl_stat=None, Tensor? go=None, float kl_thr=0.0, Tensor? kl_trace=None, int kl_step=0) -> ()");
@@ -2514,11 +2525,12 @@ TORCH_LIBRARY(acamd, m) {
         "Tensor done, Tensor truncated, Tensor log_std, Tensor ac_scale, int key_shift, int policy_seed, "
         "Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, Tensor lin_A, "
         "Tensor lin_B, int env_seed, int max_steps, int k, bool wlds, Tensor? stamps=None, Tensor? final_obs=None, "
-        "Tensor? final_step=None, Tensor? norm_tables=None, float norm_clip=0.0) -> ()");
+        "Tensor? final_step=None, Tensor? norm_tables=None, float norm_clip=0.0, bool hidden_tanh=False) -> ()");
   m.def("mlp_rollout_eval(Tensor desc, int lds, Tensor obs0, int steps, Tensor log_std, Tensor ac_scale, "
         "Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor env_ids, Tensor lin_A, Tensor lin_B, int env_seed, "
         "int max_steps, int k, bool wlds, Tensor? rec_ret, Tensor? rec_len, Tensor? rec_cnt, "
-        "Tensor? norm_tables=None, float norm_clip=0.0, Tensor? final_obs=None, Tensor? final_step=None) -> ()");
+        "Tensor? norm_tables=None, float norm_clip=0.0, Tensor? final_obs=None, Tensor? final_step=None, "
+        "bool hidden_tanh=False) -> ()");
   m.def("eval_scan_unroll() -> int", &eval_scan_unroll);
   m.def("eval_scan(Tensor rewards, Tensor dones, Tensor rec_ret, Tensor rec_len, Tensor rec_cnt) -> ()");
   m.def("obs_norm_parts(int R) -> int", &obs_norm_parts);

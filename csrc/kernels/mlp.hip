@@ -70,7 +70,9 @@ __device__ __forceinline__ int ld_of(int w) { return 16 * ngp2(w) + 4; }   // pa
 
 // Hidden-layer activations as one branch-free form y = v > 0 ? v : slope * v (relu: slope 0, lrelu(0.2) of
 // policies.py:20-21: 0.2, identity: 1); the tanh of the Gaussian head is applied by the head code itself (the
-// layer stores the pre-activation z), so the MFMA epilogues carry no per-activation branches.
+// layer stores the pre-activation z). A HIDDEN tanh layer (generic path only) is the one activation outside this
+// form: layer_fwd_t / layer_dgrad_t take a uniform branch for it; the SPEC path and the one-launch rollout know
+// the slope form only, and their launchers refuse a descriptor with a hidden ACT_TANH.
 __device__ __forceinline__ float act_slope(int act) {
   return act == ACT_RELU ? 0.f : act == ACT_LRELU ? 0.2f : 1.f;
 }
@@ -89,7 +91,10 @@ constexpr int MLP_MAXG = MLP_MAXW / 16;   // k-groups of the widest layer
 // layer). For the tanh head Y holds z (the head code applies tanh and the scale).
 // B operand from the forward fragment copy F: a lane's four B values of k-group g are 16 bytes, the wave's group one
 // contiguous 1 KB block -- all NG loads of a tile are issued before its first MFMA (one L2 round trip per tile).
-template <int NG>
+// TANH: the instantiation for towers with a hidden tanh layer (the launcher picks it from MlpArgs::hidden_tanh). Kept
+// apart because the branch measurably moved the shared epilogue (CartPole per-step update 0.100 -> 0.104 ms,
+// profiles/mlp_towers.txt); with TANH = false this is the code the reference towers always ran.
+template <int NG, bool TANH>
 __device__ void layer_fwd_t(const float* __restrict__ X, int ldx, gcf32* __restrict__ F, gcf32* __restrict__ bias,
                             int N, int act, float* __restrict__ Y, int ldy) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -122,20 +127,30 @@ __device__ void layer_fwd_t(const float* __restrict__ X, int ldx, gcf32* __restr
       __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
     }
     const float bb = bias[cc];
-    const float slope = act_slope(act);
+    // a tanh hidden layer stores tanhf(z): the code is uniform over the layer (readfirstlane: the compiler is told
+    // so), hence a scalar branch around the epilogue's stores, taken after the MFMAs
+    bool tanh_act = false;
+    if constexpr (TANH) tanh_act = __builtin_amdgcn_readfirstlane(act) == ACT_TANH;
+    if (tanh_act) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) Y[(4 * q + i) * ldy + c] = cok ? act_fwd(acc[i] + bb, slope) : 0.f;
+      for (int i = 0; i < 4; ++i) Y[(4 * q + i) * ldy + c] = cok ? tanhf(acc[i] + bb) : 0.f;
+    } else {
+      const float slope = act_slope(act);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) Y[(4 * q + i) * ldy + c] = cok ? act_fwd(acc[i] + bb, slope) : 0.f;
+    }
   }
 }
 
+template <bool TANH>
 __device__ __forceinline__ void layer_fwd(const float* X, int ldx, int K, gcf32* F, gcf32* bias, int N, int act,
                                           float* Y, int ldy) {
   switch (ngp2(K)) {
-    case 1: layer_fwd_t<1>(X, ldx, F, bias, N, act, Y, ldy); break;
-    case 2: layer_fwd_t<2>(X, ldx, F, bias, N, act, Y, ldy); break;
-    case 4: layer_fwd_t<4>(X, ldx, F, bias, N, act, Y, ldy); break;
-    case 8: layer_fwd_t<8>(X, ldx, F, bias, N, act, Y, ldy); break;
-    default: layer_fwd_t<16>(X, ldx, F, bias, N, act, Y, ldy); break;
+    case 1: layer_fwd_t<1, TANH>(X, ldx, F, bias, N, act, Y, ldy); break;
+    case 2: layer_fwd_t<2, TANH>(X, ldx, F, bias, N, act, Y, ldy); break;
+    case 4: layer_fwd_t<4, TANH>(X, ldx, F, bias, N, act, Y, ldy); break;
+    case 8: layer_fwd_t<8, TANH>(X, ldx, F, bias, N, act, Y, ldy); break;
+    default: layer_fwd_t<16, TANH>(X, ldx, F, bias, N, act, Y, ldy); break;
   }
 }
 
@@ -143,13 +158,15 @@ __device__ __forceinline__ void layer_fwd(const float* X, int ldx, int K, gcf32*
 // dPprev (LDS; every column tile up to ngp2(K) written, columns >= K as 0) and, when gdst != null, the row tile's
 // blocks of the previous layer's dP in the training workspace (blk_out layout). dP is zero-padded to 16*NG columns (NG = ngp2(N)); B operand from the data-gradient
 // fragment copy G (zero pad, so no clamped loads).
-template <int NG>
+template <int NG, bool TANH>
 __device__ void layer_dgrad_t(const float* __restrict__ dP, int ldp, gcf32* __restrict__ G, int K,
                               const float* __restrict__ Yprev, int ldyp, int act_prev, float* __restrict__ dPprev,
                               int lddp, gf32* __restrict__ gdst, int rows) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r = lane & 15, q = lane >> 4;
   const int ntile = ngp2(K);
+  bool tanh_prev = false;   // uniform over the layer: a scalar branch below
+  if constexpr (TANH) tanh_prev = __builtin_amdgcn_readfirstlane(act_prev) == ACT_TANH;
   for (int tile = wave; tile < ntile; tile += MLP_WAVES) {
     const int kc = tile * 16 + r;   // output column = input feature of the layer
     const bool kok = kc < K;
@@ -173,26 +190,41 @@ __device__ void layer_dgrad_t(const float* __restrict__ dP, int ldp, gcf32* __re
     }
     // C layout: col = lane&15 = kc, rows 4q + i -- in the workspace's block layout one 16-byte store per lane
     floatx4 o;
+    if (tanh_prev) {   // tanh' from the stored output: 1 - y^2 (exactly 0 where tanhf saturated to +-1)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int row = 4 * q + i;
-      float v = 0.f;
-      if (kok) v = acc[i] * act_bwd(Yprev[row * ldyp + kc], act_slope(act_prev));
-      dPprev[row * lddp + kc] = v;
-      o[i] = v;
+      for (int i = 0; i < 4; ++i) {
+        const int row = 4 * q + i;
+        float v = 0.f;
+        if (kok) {
+          const float y = Yprev[row * ldyp + kc];
+          v = acc[i] * (1.f - y * y);
+        }
+        dPprev[row * lddp + kc] = v;
+        o[i] = v;
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int row = 4 * q + i;
+        float v = 0.f;
+        if (kok) v = acc[i] * act_bwd(Yprev[row * ldyp + kc], act_slope(act_prev));
+        dPprev[row * lddp + kc] = v;
+        o[i] = v;
+      }
     }
     if (gdst && kok) *(__attribute__((address_space(1))) floatx4*)(gdst + tile * 256 + r * 16 + 4 * q) = o;
   }
 }
 
+template <bool TANH>
 __device__ __forceinline__ void layer_dgrad(const float* dP, int ldp, int N, gcf32* G, int K, const float* Yprev,
                                             int ldyp, int act_prev, float* dPprev, int lddp, gf32* gdst, int rows) {
   switch (ngp2(N)) {
-    case 1: layer_dgrad_t<1>(dP, ldp, G, K, Yprev, ldyp, act_prev, dPprev, lddp, gdst, rows); break;
-    case 2: layer_dgrad_t<2>(dP, ldp, G, K, Yprev, ldyp, act_prev, dPprev, lddp, gdst, rows); break;
-    case 4: layer_dgrad_t<4>(dP, ldp, G, K, Yprev, ldyp, act_prev, dPprev, lddp, gdst, rows); break;
-    case 8: layer_dgrad_t<8>(dP, ldp, G, K, Yprev, ldyp, act_prev, dPprev, lddp, gdst, rows); break;
-    default: layer_dgrad_t<16>(dP, ldp, G, K, Yprev, ldyp, act_prev, dPprev, lddp, gdst, rows); break;
+    case 1: layer_dgrad_t<1, TANH>(dP, ldp, G, K, Yprev, ldyp, act_prev, dPprev, lddp, gdst, rows); break;
+    case 2: layer_dgrad_t<2, TANH>(dP, ldp, G, K, Yprev, ldyp, act_prev, dPprev, lddp, gdst, rows); break;
+    case 4: layer_dgrad_t<4, TANH>(dP, ldp, G, K, Yprev, ldyp, act_prev, dPprev, lddp, gdst, rows); break;
+    case 8: layer_dgrad_t<8, TANH>(dP, ldp, G, K, Yprev, ldyp, act_prev, dPprev, lddp, gdst, rows); break;
+    default: layer_dgrad_t<16, TANH>(dP, ldp, G, K, Yprev, ldyp, act_prev, dPprev, lddp, gdst, rows); break;
   }
 }
 
@@ -551,7 +583,7 @@ __device__ __forceinline__ float kl_term(float x, float r) {
 // tower TW of the reference shapes in train mode, weights from registers. GREEDY (generic path, rollout launches with
 // MlpArgs::greedy): the heads return their deterministic action; an instantiation of its own, so that every other
 // launch runs the code it ran without the flag.
-template <int SPEC, int TW, bool GREEDY = false>
+template <int SPEC, int TW, bool GREEDY = false, bool TANH = false>
 __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* sm, MlpShared& S) {
   constexpr bool SP = SPEC > 0;
   using Regs = typename std::conditional<TW == 0, ActorRegs<SP ? SPEC : 1>, CriticRegs<SP ? SPEC : 1>>::type;
@@ -850,7 +882,9 @@ __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* 
     for (int l = 0; l < nl; ++l) {
       float* Yl = sm + S.yo[l];
       const int ldl = S.ld[l];
-      layer_fwd(X, ldx, S.in[l], P_<const float>(S.F[l]), P_<const float>(S.b[l]), S.out[l], S.act[l], Yl, ldl);
+      // the top layer of the Gaussian head is declared tanh, and the head applies that one itself from z
+      const int actl = (TANH && l + 1 == nl && S.act[l] == ACT_TANH) ? (int)ACT_NONE : S.act[l];
+      layer_fwd<TANH>(X, ldx, S.in[l], P_<const float>(S.F[l]), P_<const float>(S.b[l]), S.out[l], actl, Yl, ldl);
       __syncthreads();
       stamp(3 + l);
       if (a.mode == 2 && l == 0) blk_out(X0, ld0, wsp(S.xs[0], a.D), a.D);   // inputs of each layer for its
@@ -1220,7 +1254,7 @@ __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* 
     for (int l = L; l >= 1; --l) {
       const int K = S.in[l];
       gf32* gdst = wsp(S.dp[l - 1], K);
-      layer_dgrad(cur, ldP, S.out[l], P_<const float>(S.G[l]), K, sm + S.yo[l - 1], S.ld[l - 1], S.act[l - 1], nxt,
+      layer_dgrad<TANH>(cur, ldP, S.out[l], P_<const float>(S.G[l]), K, sm + S.yo[l - 1], S.ld[l - 1], S.act[l - 1], nxt,
                   ldP, gdst, rows);
       __syncthreads();
       stamp(9 + L - l);
@@ -1232,7 +1266,7 @@ __device__ __forceinline__ void mlp_tower(const MlpArgs& a, const int t, float* 
   cstamp(13);
 }
 
-template <int SPEC, bool GREEDY = false>
+template <int SPEC, bool GREEDY = false, bool TANH = false>
 __global__ void __launch_bounds__(MLP_THREADS) mlp_fwd_kernel(MlpArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // 16-byte base: the b128 LDS reads stay aligned
   __shared__ MlpShared S;
@@ -1241,7 +1275,7 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_fwd_kernel(MlpArgs a) {
   if (a.go && *a.go == 0) return;
   const int t = blockIdx.y + a.tw_base;
   if constexpr (SPEC == 0) {
-    mlp_tower<0, -1, GREEDY>(a, t, sm, S);
+    mlp_tower<0, -1, GREEDY, TANH>(a, t, sm, S);
   } else {
     if (t == 0) mlp_tower<SPEC, 0>(a, 0, sm, S);
     else mlp_tower<SPEC, 1>(a, 1, sm, S);
@@ -1935,12 +1969,35 @@ extern "C" hipError_t aca_mlp_fwd(const MlpArgs* a, int ntw, size_t lds, int spe
   if (a->B <= 0) return hipSuccess;
   if (a->A > MLP_MAXA || a->D > MLP_MAXW || ntw < 1 || a->tw_base + ntw > 2 || !a->tw) return hipErrorInvalidValue;
   if (spec && (a->mode != 2 || a->tw_base != 0 || ntw != 2 || mlp_ngp2(a->D) != spec)) return hipErrorInvalidValue;
+  // the SPEC path knows the slope activations only: a hidden tanh layer (any layer below a tower's top) is refused
+  if (spec)
+    for (int t = 0; t < 2; ++t)
+      for (int l = 0; l + 1 < (int)a->htw[t].nl && l + 1 < MLP_MAXL; ++l)
+        if (a->htw[t].act[l] == ACT_TANH) return hipErrorInvalidValue;
   // observation tables: both or none, and never with a train launch (its rows are normalised already)
   if ((a->norm_mean != nullptr) != (a->norm_istd != nullptr) || (a->norm_mean && a->mode == 2))
     return hipErrorInvalidValue;
   if (a->go && a->mode != 2) return hipErrorInvalidValue;   // the early-stop flag gates train launches only
   // deterministic actions: rollout launches of the generic kernel only, in an instantiation of their own
   if (a->greedy && (a->mode != 0 || spec != 0)) return hipErrorInvalidValue;
+  // towers with a hidden tanh layer: the generic kernel's TANH instantiations (never the SPEC path)
+  if (a->hidden_tanh) {
+    if (spec != 0) return hipErrorInvalidValue;
+    static bool tattr = false;
+    if (!tattr) {
+      const void* ks[2] = {reinterpret_cast<const void*>(&mlp_fwd_kernel<0, false, true>),
+                           reinterpret_cast<const void*>(&mlp_fwd_kernel<0, true, true>)};
+      for (const void* k : ks)
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) != hipSuccess)
+          return hipErrorInvalidValue;
+      tattr = true;
+    }
+    if (lds > 140 * 1024) return hipErrorInvalidValue;
+    const dim3 tgrid((a->B + MLP_BM - 1) / MLP_BM, ntw);
+    if (a->greedy) mlp_fwd_kernel<0, true, true><<<tgrid, MLP_THREADS, lds, stream>>>(*a);
+    else mlp_fwd_kernel<0, false, true><<<tgrid, MLP_THREADS, lds, stream>>>(*a);
+    return hipGetLastError();
+  }
   if (a->greedy) {
     static bool gattr = false;
     if (!gattr) {
@@ -2008,6 +2065,7 @@ extern "C" hipError_t aca_mlp_rollout(const RolloutArgs* a, size_t lds, hipStrea
   if (a->N <= 0 || a->T <= 0) return hipSuccess;
   if (!a->tw || a->head != 2 || a->A != LIN_ACT || a->k < 1 || a->k > 3 || a->D != LIN_OBS * a->k || !a->wlds)
     return hipErrorInvalidValue;
+  if (a->hidden_tanh) return hipErrorInvalidValue;   // slope activations only (relu / lrelu / identity)
   // terminal observations: an env that enters with t < max_steps truncates at most ceil(T / max_steps) times
   const bool boot = a->final_obs != nullptr;
   if (boot && (!a->final_step || a->max_steps < 1 ||

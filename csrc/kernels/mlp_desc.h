@@ -67,6 +67,9 @@ struct MlpArgs {
   // the fixed-order sum of -log_std - HALF_LOG_2PI), the categorical head the first index of the largest logit
   // (torch.argmax's tie rule); no key is hashed. Entropy and value are those of the sampling launch.
   int greedy;
+  // set by the owner of the (device-resident) descriptor when a hidden layer of either tower is tanh: the launcher
+  // then takes the generic kernel's TANH instantiations (the others know the slope activations only)
+  int hidden_tanh;
 };
 
 struct WgradArgs {
@@ -139,6 +142,9 @@ struct RolloutArgs {
   float* ev_ret; int32_t* ev_len;   // [N][E]
   int32_t* ev_cnt;                  // [N]
   int E;
+  // set by the owner of the (device-resident) descriptor when a hidden layer of the actor is tanh: the kernel's layers
+  // have the slope activations only, so the launcher refuses the launch
+  int hidden_tanh;
 };
 
 }  // namespace aca

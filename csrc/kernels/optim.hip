@@ -235,7 +235,9 @@ __device__ __forceinline__ void opt_ticket(const OptSeg& S, int vblk, int vgrid,
 //           w updates rows 4 w + (lane >> 4), columns 4 (lane & 15) .. + 3 (whole 256-byte row runs), the new values
 //           go through the workgroup's LDS tile, then wave w stores the 1 KB F block of column tile w (at
 //           F = w4 + w * w6 floats) and the 1 KB G block (at G = w5 + 256 w floats, w5 = 0: none)
-//   type 2: a whole small [K][N] weight at e0 (K = w2, N = w3, K * N <= 4 * OPT_THREADS), F / G written per element
+//   type 2: a whole small [K][N] weight at e0 (K = w2, N = w3, K * N <= 4 * OPT_THREADS), F / G written per element;
+//           or, with w7 != 0, w2 <= 4 * OPT_THREADS elements from element w6 of a larger [w7][N] weight (e0 = the
+//           weight's offset + w6): a weight whose N is no multiple of 64 and that one workgroup cannot hold
 template <bool ADAM>
 __device__ __forceinline__ void opt_items(const OptSeg& S, float b1, float b2, float eps, int zero_grad, int vblk,
                                           int vgrid, float* shr, float* blks) {
@@ -267,7 +269,7 @@ __device__ __forceinline__ void opt_items(const OptSeg& S, float b1, float b2, f
       x4[3][0] = ADAM ? reinterpret_cast<const float4*>(m)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
   } else {
-    const int tot = type == 0 ? n : n * N;
+    const int tot = (type == 0 || rec[7]) ? n : n * N;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       if (tid + OPT_THREADS * j < tot) {
@@ -360,8 +362,9 @@ __device__ __forceinline__ void opt_items(const OptSeg& S, float b1, float b2, f
         p[i] = pi;
         if (shadow) shadow[i] = f2bf(pi);
         if (type == 2) {
-          const uint32_t o = (uint32_t)(tid + OPT_THREADS * j), k = o / (uint32_t)N, c = o - k * (uint32_t)N;
-          F[mlp_frag_f(k, c, n)] = pi;
+          const uint32_t o = (uint32_t)rec[6] + (uint32_t)(tid + OPT_THREADS * j), k = o / (uint32_t)N,
+                         c = o - k * (uint32_t)N;
+          F[mlp_frag_f(k, c, rec[7] ? (int)rec[7] : n)] = pi;
           if (G) G[mlp_frag_g(k, c, N)] = pi;
         }
       }
