@@ -15,9 +15,12 @@ On GPU the trainers use :func:`returns_scan`: ONE HIP launch (``returns_scan_ker
 env) -- both are affine recurrences ``x_t = a_t + c_t x_{t+1}`` -- together with the EV-before correlation, the
 moments a data-parallel run all-reduces, and (optionally) the in-place advantage normalisation. The truncated
 n-step window (``L < T``) uses its prefix-sum form (scan of the un-bootstrapped return + next-terminal index). The
-simple per-column kernels (:func:`gae`, :func:`nstep_returns`) stay as the small-T building blocks. The PyTorch
-code below is the oracle all of them are tested against; ``tests/oracles/returns_oracle.py`` is the independent fp64
-oracle (fp32-rounded ``gamma`` / ``lambda``, derived tolerances) that pins every kernel, and this code, at the edges.
+simple per-column kernels (:func:`gae`, :func:`nstep_returns`) stay as the small-T building blocks. On the device
+the maths of all of them -- and of the returns computed inside the loss and head kernels -- is stated once, in
+``csrc/kernels/returns_math.h`` (recurrence steps, per-point returns, moments, EV correlation, normalisation
+constants). The PyTorch code below is the oracle all of them are tested against;
+``tests/oracles/returns_oracle.py`` is the independent fp64 oracle (fp32-rounded ``gamma`` / ``lambda``, derived
+tolerances) that pins every kernel, and this code, at the edges.
 """
 from __future__ import annotations
 

@@ -14,15 +14,19 @@
 // One workgroup: the stats reduction is deterministic.
 //
 // A2C fast path (returns_mode 1 = n-step / 2 = GAE): the kernel first computes the targets and advantages of the
-// whole [T, N] rollout itself (same maths as returns.hip), the EV-before statistic (stats[7], Basic_AC/util.py:4-12)
-// and, with norm_adv, the population-std advantage normalisation (Basic_AC/run_AC.py:241) -- the returns, EV and
-// normalisation kernels of the generic path fold into this one launch. dbias (optional) receives the column sums of
-// dz = the gradient of the head bias, written directly (the gradient slab is clean).
+// whole [T, N] rollout itself, the EV-before statistic (stats[7]) and, with norm_adv, the population-std advantage
+// normalisation -- the returns, EV and normalisation kernels of the generic path fold into this one launch; that
+// maths is stated once, in returns_math.h (point_return, accum_ret_moments, ev_corr, adv_norm), for this kernel, the
+// three head kernels below and returns.hip. dbias (optional) receives the column sums of dz = the gradient of the
+// head bias, written directly (the gradient slab is clean).
 #include "common.h"
 #include "cnn_head.h"
 #include "launch_api.h"
+#include "returns_math.h"
 
 namespace aca {
+
+constexpr float ADV_EPS = 1e-8f;   // eps of the in-kernel advantage normalisation (Basic_AC/run_AC.py:241)
 
 // threads of ac_loss_kernel: the categorical specialisations run 16 waves (a B = 4096 PPO minibatch is 4 row
 // iterations per thread, not 16 -- each iteration is a dependent memory round trip); the generic form (runtime A,
@@ -69,55 +73,24 @@ __global__ void __launch_bounds__(loss_threads<AC>()) ac_loss_kernel(LossArgs a)
   float adv_mean = 0.f, adv_inv = 1.f;
   if (a.returns_mode) {
     // ---- phase 0: targets / advantages of every (t, n), EV-before, normalisation constants
-    double s_r = 0, s_rr = 0, s_v = 0, s_vv = 0, s_rv = 0, s_a = 0, s_aa = 0;
+    double m[7] = {0, 0, 0, 0, 0, 0, 0};   // adv, adv^2, ret, ret^2, V, V^2, ret*V
     for (int idx = threadIdx.x; idx < a.B; idx += blockDim.x) {
       const int t = idx / a.N, n = idx - t * a.N;
-      float R;
-      if (a.returns_mode == 1) {
-        const int h = min(t + a.L, a.T);
-        float acc = 0.f, disc = 1.f;
-        bool alive = true;
-        for (int k = t; k < h; ++k) {
-          const int i = k * a.N + n;
-          acc += disc * rew[i];
-          disc *= a.gamma;
-          if (dn[i]) { alive = false; break; }
-        }
-        if (alive) acc += disc * val[h * a.N + n];
-        R = acc;
-      } else {
-        float last = 0.f;
-        for (int k = a.T - 1; k >= t; --k) {
-          const int i = k * a.N + n;
-          const float nd = dn[i] ? 0.f : 1.f;
-          const float delta = rew[i] + a.gamma * val[i + a.N] * nd - val[i];
-          last = delta + a.gamma * a.lam * nd * last;
-        }
-        R = last + val[idx];
-      }
+      const float R = point_return(a.returns_mode, rew, dn, val, t, a.T, a.L, a.gamma, a.lam, a.N, n);
       const float v = val[idx];
       const float A_ = R - v;
       a.ret_w[idx] = R;
       a.adv_w[idx] = A_;
       if (staged) { s_ret[idx] = R; s_adv[idx] = A_; }
-      s_r += R; s_rr += (double)R * R; s_v += v; s_vv += (double)v * v; s_rv += (double)R * v;
-      s_a += A_; s_aa += (double)A_ * A_;
+      accum_ret_moments(m, R, A_, v);
     }
     if (!staged) __threadfence_block();   // global ret_w / adv_w are re-read by other threads after the barrier
-    double red[7] = {s_r, s_rr, s_v, s_vv, s_rv, s_a, s_aa};
-    block_sum_multi<7>(red, sh);   // ends with a barrier: s_ret / s_adv (or the global scratch) are complete
-    s_r = red[0]; s_rr = red[1]; s_v = red[2]; s_vv = red[3]; s_rv = red[4]; s_a = red[5]; s_aa = red[6];
-    const double n = a.B;
-    if (threadIdx.x == 0) {
-      const double mr = s_r / n, mv = s_v / n;
-      const double vr = fmax(s_rr / n - mr * mr, 0.0), vv = fmax(s_vv / n - mv * mv, 0.0);
-      a.stats[7] = (float)((s_rv / n - mr * mv) / sqrt(vr * vv));
-    }
+    block_sum_multi<7>(m, sh);   // ends with a barrier: s_ret / s_adv (or the global scratch) are complete
+    if (threadIdx.x == 0) a.stats[7] = ev_corr(m[2], m[3], m[4], m[5], m[6], a.B);
     if (a.norm_adv) {
-      const double m = s_a / n;
-      const double var = fmax(s_aa / n - m * m, 0.0);
-      adv_mean = (float)m;
-      adv_inv = 1.0f / (1e-8f + (float)sqrt(var));
+      const AdvNorm c = adv_norm(m[0], m[1], a.B, ADV_EPS);
+      adv_mean = c.mean;
+      adv_inv = c.inv;
     }
   }
   const float* advp = a.returns_mode ? (staged ? s_adv : a.adv_w) : a.adv;
@@ -355,33 +328,11 @@ __global__ void __launch_bounds__(HB_THREADS) head_bwd_kernel(HeadBwdArgs a) {
   const float c_ent = *a.ent_coef, beta = *a.kl_coef;
   __syncthreads();
   hb_stamp(a, 1);
-  // ---- returns, EV-before, advantage statistics (same maths as ac_loss_kernel phase 0)
-  double s_r = 0, s_rr = 0, s_v = 0, s_vv = 0, s_rv = 0, s_a = 0, s_aa = 0;
+  // ---- returns, EV-before, advantage statistics (returns_math.h)
+  double m[7] = {0, 0, 0, 0, 0, 0, 0};   // adv, adv^2, ret, ret^2, V, V^2, ret*V
   if (row) {
     const int idx = tid, t = idx / a.N, n = idx - t * a.N;
-    float R;
-    if (a.returns_mode == 1) {
-      const int hh = min(t + a.L, a.T);
-      float acc = 0.f, disc = 1.f;
-      bool alive = true;
-      for (int k = t; k < hh; ++k) {
-        const int i = k * a.N + n;
-        acc += disc * s_rew[i];
-        disc *= a.gamma;
-        if (s_dn[i]) { alive = false; break; }
-      }
-      if (alive) acc += disc * s_val[hh * a.N + n];
-      R = acc;
-    } else {
-      float last = 0.f;
-      for (int k = a.T - 1; k >= t; --k) {
-        const int i = k * a.N + n;
-        const float nd = s_dn[i] ? 0.f : 1.f;
-        const float delta = s_rew[i] + a.gamma * s_val[i + a.N] * nd - s_val[i];
-        last = delta + a.gamma * a.lam * nd * last;
-      }
-      R = last + s_val[idx];
-    }
+    const float R = point_return(a.returns_mode, s_rew, s_dn, s_val, t, a.T, a.L, a.gamma, a.lam, a.N, n);
     const float v = s_val[idx], A_ = R - v;
     if (lead) {
       a.ret_w[idx] = R;
@@ -389,23 +340,16 @@ __global__ void __launch_bounds__(HB_THREADS) head_bwd_kernel(HeadBwdArgs a) {
     }
     s_ret[idx] = R;
     s_adv[idx] = A_;
-    s_r = R; s_rr = (double)R * R; s_v = v; s_vv = (double)v * v; s_rv = (double)R * v; s_a = A_;
-    s_aa = (double)A_ * A_;
+    accum_ret_moments(m, R, A_, v);
   }
-  double red[7] = {s_r, s_rr, s_v, s_vv, s_rv, s_a, s_aa};
-  block_sum_multi<7>(red, sh);
+  block_sum_multi<7>(m, sh);
   hb_stamp(a, 2);
-  const double nB = B;
-  if (lead && tid == 0) {
-    const double mr = red[0] / nB, mv = red[2] / nB;
-    const double vr = fmax(red[1] / nB - mr * mr, 0.0), vv = fmax(red[3] / nB - mv * mv, 0.0);
-    a.stats[7] = (float)((red[4] / nB - mr * mv) / sqrt(vr * vv));
-  }
+  if (lead && tid == 0) a.stats[7] = ev_corr(m[2], m[3], m[4], m[5], m[6], B);
   float adv_mean = 0.f, adv_inv = 1.f;
   if (a.norm_adv) {
-    const double m = red[5] / nB, var = fmax(red[6] / nB - m * m, 0.0);
-    adv_mean = (float)m;
-    adv_inv = 1.0f / (1e-8f + (float)sqrt(var));
+    const AdvNorm c = adv_norm(m[0], m[1], B, ADV_EPS);
+    adv_mean = c.mean;
+    adv_inv = c.inv;
   }
   // ---- loss + dz (A2C: PG + KL proxy + entropy; value MSE)
   const float invB = 1.0f / (float)B;
@@ -659,35 +603,13 @@ __global__ void __launch_bounds__(AH_THREADS) a2c_head_kernel(A2cHeadArgs args) 
   __syncthreads();
   hb_stamp(a, 1);
   // ---- returns, advantage moments (+ EV-before sums on workgroup 0)
-  double s_r = 0, s_rr = 0, s_v = 0, s_vv = 0, s_rv = 0, s_a = 0, s_aa = 0;
+  double m[7] = {0, 0, 0, 0, 0, 0, 0};   // adv, adv^2, ret, ret^2, V, V^2, ret*V (returns_math.h)
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     const int idx = tid + k * AH_THREADS;
     if (idx < B) {
       const int t = idx / N, n = idx - t * N;
-      float R;
-      if (a.returns_mode == 1) {
-        const int hh = min(t + a.L, a.T);
-        float acc = 0.f, disc = 1.f;
-        bool alive = true;
-        for (int q = t; q < hh; ++q) {
-          const int i = q * N + n;
-          acc += disc * s_rew[i];
-          disc *= a.gamma;
-          if (s_dn[i]) { alive = false; break; }
-        }
-        if (alive) acc += disc * s_val[hh * N + n];
-        R = acc;
-      } else {
-        float last = 0.f;
-        for (int q = a.T - 1; q >= t; --q) {
-          const int i = q * N + n;
-          const float nd = s_dn[i] ? 0.f : 1.f;
-          const float delta = s_rew[i] + a.gamma * s_val[i + N] * nd - s_val[i];
-          last = delta + a.gamma * a.lam * nd * last;
-        }
-        R = last + s_val[idx];
-      }
+      const float R = point_return(a.returns_mode, s_rew, s_dn, s_val, t, a.T, a.L, a.gamma, a.lam, N, n);
       const float v = s_val[idx], A_ = R - v;
       if (lead) {
         a.ret_w[idx] = R;
@@ -695,33 +617,24 @@ __global__ void __launch_bounds__(AH_THREADS) a2c_head_kernel(A2cHeadArgs args) 
       }
       s_ret[idx] = R;
       s_adv[idx] = A_;
-      s_r += R; s_rr += (double)R * R; s_v += v; s_vv += (double)v * v; s_rv += (double)R * v; s_a += A_;
-      s_aa += (double)A_ * A_;
+      accum_ret_moments(m, R, A_, v);
     }
   }
-  const double nB = B;
   float adv_mean = 0.f, adv_inv = 1.f;
   if (ev_wg) {
-    double red[7] = {s_a, s_aa, s_r, s_rr, s_v, s_vv, s_rv};
-    block_sum_multi<7>(red, sh);
-    if (tid == 0) {
-      const double mr = red[2] / nB, mv = red[4] / nB;
-      const double vr = fmax(red[3] / nB - mr * mr, 0.0), vv = fmax(red[5] / nB - mv * mv, 0.0);
-      a.stats[7] = (float)((red[6] / nB - mr * mv) / sqrt(vr * vv));
-    }
-    s_a = red[0];
-    s_aa = red[1];
+    block_sum_multi<7>(m, sh);
+    if (tid == 0) a.stats[7] = ev_corr(m[2], m[3], m[4], m[5], m[6], B);
   } else {
-    double red[2] = {s_a, s_aa};   // the same per-value tree as the lead's: bit-identical moments
+    double red[2] = {m[0], m[1]};   // the same per-value tree as the EV workgroup's: bit-identical moments
     block_sum_multi<2>(red, sh);
-    s_a = red[0];
-    s_aa = red[1];
+    m[0] = red[0];
+    m[1] = red[1];
   }
   hb_stamp(a, 2);
   if (a.norm_adv) {
-    const double m = s_a / nB, var = fmax(s_aa / nB - m * m, 0.0);
-    adv_mean = (float)m;
-    adv_inv = 1.0f / (1e-8f + (float)sqrt(var));
+    const AdvNorm c = adv_norm(m[0], m[1], B, ADV_EPS);
+    adv_mean = c.mean;
+    adv_inv = c.inv;
   }
   // ---- loss + dz
   const float invB = 1.0f / (float)B;
@@ -957,27 +870,8 @@ __global__ void __launch_bounds__(AE_THREADS) a2c_head_env_kernel(A2cEnvArgs arg
   double st[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   if (tid < T) {
     const int t = tid;
-    float R;
-    if (a.returns_mode == 1) {
-      const int hh = min(t + a.L, T);
-      float acc = 0.f, disc = 1.f;
-      bool alive = true;
-      for (int q = t; q < hh; ++q) {
-        acc += disc * s_rew[q];
-        disc *= a.gamma;
-        if (s_dn[q]) { alive = false; break; }
-      }
-      if (alive) acc += disc * s_val[hh];
-      R = acc;
-    } else {
-      float last = 0.f;
-      for (int q = T - 1; q >= t; --q) {
-        const float nd = s_dn[q] ? 0.f : 1.f;
-        const float delta = s_rew[q] + a.gamma * s_val[q + 1] * nd - s_val[q];
-        last = delta + a.gamma * a.lam * nd * last;
-      }
-      R = last + s_val[t];
-    }
+    // this env's column, staged contiguously: stride 1, column 0 (returns_math.h)
+    const float R = point_return(a.returns_mode, s_rew, s_dn, s_val, t, T, a.L, a.gamma, a.lam, 1, 0);
     const float v = s_val[t], adv = R - v;
     const int64_t row = (int64_t)t * N + e;
     a.ret_w[row] = R;

@@ -1,14 +1,14 @@
-// Return / advantage estimators over [T, N] rollouts and small statistics (K12).
-//
-// * gae:    reverse scan per env column, A_t = delta_t + gamma*lambda*(1-d_t)*A_{t+1}; R_t = A_t + V_t.
-// * nstep:  PathAdv generalised to [T, N] (Basic_AC/run_AC.py:55-80): window [t, min(t+L, T)),
-//           discounted reward sum that stops at the first terminal transition, bootstrap gamma^(h-t) V[h] only if
-//           the window did not end in a terminal. One thread per (t, n).
-// * normalize_adv: (A - mean) / (1e-8 + std_pop) (Basic_AC/run_AC.py:241), one workgroup, fp64 sums.
-// * moments: sum, sum of squares of x and y and cross term (EV correlation Basic_AC/util.py:4-12).
-// Oracles: ops/returns.py, utils/stats.py.
+// Return / advantage estimators over [T, N] rollouts and small statistics (K12). The maths --
+// the GAE and n-step steps, the per-point returns, the moments, the EV correlation and the advantage-normalisation
+// constants -- is stated once, in returns_math.h; the kernels here are its launch shapes:
+// * gae:    reverse sweep per env column, one thread per column.
+// * nstep:  one thread per (t, n) (PathAdv generalised to [T, N], Basic_AC/run_AC.py:55-80).
+// * normalize_adv, moments, ev: one workgroup, fp64 sums; ev_multi / normalize_mom: the many-workgroup forms.
+// * returns_scan: either estimator as a chunked associative scan, fused with the statistics (below).
+// Oracles: ops/returns.py, utils/stats.py; tests/oracles/returns_oracle.py pins every kernel at its edges.
 #include "common.h"
 #include "launch_api.h"
+#include "returns_math.h"
 
 namespace aca {
 
@@ -19,9 +19,7 @@ __global__ void gae_kernel(const float* __restrict__ r, const float* __restrict_
   float last = 0.f;
   for (int t = T - 1; t >= 0; --t) {
     const size_t i = (size_t)t * N + n;
-    const float nd = d[i] ? 0.f : 1.f;
-    const float delta = r[i] + gamma * v[i + N] * nd - v[i];
-    last = delta + gamma * lam * nd * last;
+    last = gae_step<float>(r[i], v[i], v[i + N], d[i], gamma, gamma * lam, last);
     adv[i] = last;
     ret[i] = last + v[i];
   }
@@ -31,17 +29,7 @@ __global__ void nstep_kernel(const float* __restrict__ r, const float* __restric
                              float* __restrict__ tgt, float* __restrict__ adv, int T, int N, float gamma, int L) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= T * N) return;
-  const int t = idx / N, n = idx % N;
-  const int h = min(t + L, T);
-  float acc = 0.f, disc = 1.f;
-  bool alive = true;
-  for (int k = t; k < h; ++k) {
-    const size_t i = (size_t)k * N + n;
-    acc += disc * r[i];
-    disc *= gamma;
-    if (d[i]) { alive = false; break; }
-  }
-  if (alive) acc += disc * v[(size_t)h * N + n];
+  const float acc = nstep_point(r, d, v, idx / N, T, L, gamma, N, idx % N);
   tgt[idx] = acc;
   adv[idx] = acc - v[idx];
 }
@@ -57,43 +45,36 @@ __global__ void __launch_bounds__(1024) normalize_kernel(const float* __restrict
   }
   s = block_sum_d(s, sh);
   s2 = block_sum_d(s2, sh);
-  const double mean = s / n;
-  const double var = fmax(s2 / n - mean * mean, 0.0);
-  const float fm = (float)mean, inv = 1.0f / (eps + (float)sqrt(var));
-  for (int i = threadIdx.x; i < n; i += blockDim.x) out[i] = (a[i] - fm) * inv;
+  const AdvNorm c = adv_norm(s, s2, n, eps);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) out[i] = (a[i] - c.mean) * c.inv;
+}
+
+// one workgroup's (sum x, sum x^2, sum y, sum y^2, sum x*y), fp64, valid in every thread
+__device__ __forceinline__ void block_pair_moments(const float* __restrict__ x, const float* __restrict__ y, int n,
+                                                   double (&m)[5], double* sh) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) accum_pair_moments(m, x[i], y[i]);
+#pragma unroll
+  for (int k = 0; k < 5; ++k) m[k] = block_sum_d(m[k], sh);
 }
 
 // out[0..4] = sum x, sum x^2, sum y, sum y^2, sum x*y  (fp64 accumulation, fp32 results)
 __global__ void __launch_bounds__(1024) moments_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                        float* __restrict__ out, int n) {
   __shared__ double sh[16];
-  double a = 0, b = 0, c = 0, dd = 0, e = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const double xi = x[i], yi = y[i];
-    a += xi; b += xi * xi; c += yi; dd += yi * yi; e += xi * yi;
-  }
-  a = block_sum_d(a, sh); b = block_sum_d(b, sh); c = block_sum_d(c, sh);
-  dd = block_sum_d(dd, sh); e = block_sum_d(e, sh);
-  if (threadIdx.x == 0) { out[0] = a; out[1] = b; out[2] = c; out[3] = dd; out[4] = e; }
+  double m[5] = {0, 0, 0, 0, 0};
+  block_pair_moments(x, y, n, m, sh);
+  if (threadIdx.x == 0)
+#pragma unroll
+    for (int k = 0; k < 5; ++k) out[k] = m[k];
 }
 
-// EV correlation of the reference (Basic_AC/util.py:4-12): mean(z(x) * z(y)), population std, written to *out.
+// EV correlation (returns_math.h ev_corr) of x and y, written to *out.
 __global__ void __launch_bounds__(1024) ev_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                   float* __restrict__ out, int n) {
   __shared__ double sh[16];
-  double a = 0, b = 0, c = 0, dd = 0, e = 0;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) {
-    const double xi = x[i], yi = y[i];
-    a += xi; b += xi * xi; c += yi; dd += yi * yi; e += xi * yi;
-  }
-  a = block_sum_d(a, sh); b = block_sum_d(b, sh); c = block_sum_d(c, sh);
-  dd = block_sum_d(dd, sh); e = block_sum_d(e, sh);
-  if (threadIdx.x == 0) {
-    const double mx = a / n, my = c / n;
-    const double vx = b / n - mx * mx, vy = dd / n - my * my;
-    const double cov = e / n - mx * my;
-    *out = (float)(cov / sqrt(fmax(vx, 0.0) * fmax(vy, 0.0)));
-  }
+  double m[5] = {0, 0, 0, 0, 0};
+  block_pair_moments(x, y, n, m, sh);
+  if (threadIdx.x == 0) *out = ev_corr(m[0], m[1], m[2], m[3], m[4], n);
 }
 
 // PPO minibatch permutation of one epoch (csrc/kernels/common.h prp_index; oracle envs/rng.py prp)
@@ -119,6 +100,19 @@ __global__ void __launch_bounds__(256) mb_gather_kernel(const uint8_t* __restric
                                                         unsigned int* __restrict__ bump_ticket,
                                                         int64_t* __restrict__ o_idx, int mb) {
   const int64_t ucv = *uc;
+  // the per-row scalars of minibatch row i, from batch row src
+  auto gather_row_scalars = [&](int i, uint32_t src) {
+    float a_ = adv[src];
+    if (mom) {   // advantage normalisation deferred from the returns scan (population std, fp64 totals)
+      const AdvNorm c = adv_norm(mom[1], mom[2], mom[0], eps);
+      a_ = (a_ - c.mean) * c.inv;
+    }
+    o_act[i] = act[src];
+    o_logp[i] = logp[src];
+    o_adv[i] = a_;
+    o_ret[i] = ret[src];
+    o_v[i] = v[src];
+  };
   if (o_idx) {
     // index mode (o_obs null): one thread per row writes the source row index instead of copying the observation;
     // the minibatch's trunk forward and conv1 weight gradient read obs[o_idx[i]] directly (one 28 KB copy per row
@@ -126,17 +120,8 @@ __global__ void __launch_bounds__(256) mb_gather_kernel(const uint8_t* __restric
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < mb) {
       const uint32_t src = prp_index((uint32_t)(off + i), (uint32_t)n, minibatch_key(seed, ucv, ep));
-      float a_ = adv[src];
-      if (mom) {
-        const double cnt = mom[0], mean = mom[1] / cnt, var = fmax(mom[2] / cnt - mean * mean, 0.0);
-        a_ = (a_ - (float)mean) * (1.0f / (eps + (float)sqrt(var)));
-      }
       o_idx[i] = src;
-      o_act[i] = act[src];
-      o_logp[i] = logp[src];
-      o_adv[i] = a_;
-      o_ret[i] = ret[src];
-      o_v[i] = v[src];
+      gather_row_scalars(i, src);
     }
   } else {
   const int i = blockIdx.x;
@@ -156,18 +141,7 @@ __global__ void __launch_bounds__(256) mb_gather_kernel(const uint8_t* __restric
   } else {
     for (int64_t j = threadIdx.x; j < R; j += 256) d[j] = s[j];
   }
-  if (threadIdx.x == 0) {
-    float a_ = adv[src];
-    if (mom) {   // advantage normalisation deferred from the returns scan (population std, fp64 totals)
-      const double cnt = mom[0], mean = mom[1] / cnt, var = fmax(mom[2] / cnt - mean * mean, 0.0);
-      a_ = (a_ - (float)mean) * (1.0f / (eps + (float)sqrt(var)));
-    }
-    o_act[i] = act[src];
-    o_logp[i] = logp[src];
-    o_adv[i] = a_;
-    o_ret[i] = ret[src];
-    o_v[i] = v[src];
-  }
+  if (threadIdx.x == 0) gather_row_scalars(i, src);
   }
   if (bump_ticket) {
     // last minibatch of the update: the workgroup that finishes last advances the update counter. Only a count is
@@ -280,35 +254,33 @@ __global__ void __launch_bounds__(RS_THREADS) returns_scan_kernel(RetScanArgs a)
       cd[u] = a.d[i];
     }
   }
+  // one step's operands, widened: the u-th register copy, or global loads (V_t only where the pass uses it)
+  struct Step { double r, v, vn; bool dn; };
+  auto from_regs = [&](int u) { return Step{cr[u], cv[u], cvn[u], cd[u] != 0}; };
+  auto from_global = [&](int t, bool want_v) {
+    const size_t i = (size_t)t * N + n;
+    return Step{a.r[i], want_v ? a.v[i] : 0.f, gae ? a.v[i + N] : 0.f, a.d[i] != 0};
+  };
+  // body(t, step) over the thread's chunk, last step first
+  auto for_chunk_reversed = [&](bool want_v, auto body) {
+    if (live && regs) {
+#pragma unroll
+      for (int u = 0; u < RS_KREG; ++u) {
+        const int t = t1 - 1 - u;
+        if (t >= t0) body(t, from_regs(u));
+      }
+    } else if (live) {
+      for (int t = t1 - 1; t >= t0; --t) body(t, from_global(t, want_v));
+    }
+  };
   // pass 1: chunk map x_{t0} = ca + cc x_{t1}, first terminal index in the chunk
   double ca = 0.0, cc = 1.0;
   int ft = T;
-  if (live && regs) {
-#pragma unroll
-    for (int u = 0; u < RS_KREG; ++u) {
-      const int t = t1 - 1 - u;
-      if (t >= t0) {
-        const bool dn = cd[u] != 0;
-        const double nd = dn ? 0.0 : 1.0;
-        ft = dn ? t : ft;
-        const double x = gae ? (double)cr[u] + g * (double)cvn[u] * nd - (double)cv[u] : (double)cr[u];
-        const double c = (gae ? gl : g) * nd;
-        ca = x + c * ca;
-        cc = c * cc;
-      }
-    }
-  } else if (live) {
-    for (int t = t1 - 1; t >= t0; --t) {
-      const size_t i = (size_t)t * N + n;
-      const bool dn = a.d[i] != 0;
-      const double nd = dn ? 0.0 : 1.0;
-      ft = dn ? t : ft;
-      const double x = gae ? (double)a.r[i] + g * (double)a.v[i + N] * nd - (double)a.v[i] : (double)a.r[i];
-      const double c = (gae ? gl : g) * nd;
-      ca = x + c * ca;
-      cc = c * cc;
-    }
-  }
+  for_chunk_reversed(gae, [&](int t, Step s) {
+    ft = s.dn ? t : ft;
+    ca = gae ? gae_step(s.r, s.v, s.vn, s.dn, g, gl, ca) : nstep_step(s.r, s.dn, g, ca);
+    cc = (gae ? gl : g) * not_done<double>(s.dn) * cc;
+  });
   // suffix scan over the chunks of each env: F_ch = f_ch o F_{ch+1}
   double x = init;
   int ntc = T;
@@ -343,46 +315,19 @@ __global__ void __launch_bounds__(RS_THREADS) returns_scan_kernel(RetScanArgs a)
   double m[RS_MOM];
 #pragma unroll
   for (int k = 0; k < RS_MOM; ++k) m[k] = 0.0;
-  if (live && regs) {
-#pragma unroll
-    for (int u = 0; u < RS_KREG; ++u) {
-      const int t = t1 - 1 - u;
-      if (t < t0) continue;
-      const size_t i = (size_t)t * N + n;
-      const double nd = cd[u] ? 0.0 : 1.0;
-      const double vt = cv[u];
-      if (gae) x = (double)cr[u] + g * (double)cvn[u] * nd - vt + gl * nd * x;
-      else x = (double)cr[u] + g * nd * x;
-      if (window) {
-        a.gz[i] = x;
-        continue;
-      }
-      const double rt = gae ? x + vt : x, ad = gae ? x : x - vt;
-      const float rf = (float)rt, af = (float)ad;
-      a.ret[i] = rf;
-      a.adv[i] = af;
-      m[0] += af; m[1] += (double)af * af; m[2] += rf; m[3] += (double)rf * rf;
-      m[4] += vt; m[5] += vt * vt; m[6] += (double)rf * vt;
-    }
-  } else if (live) {
-    for (int t = t1 - 1; t >= t0; --t) {
-      const size_t i = (size_t)t * N + n;
-      const double nd = a.d[i] ? 0.0 : 1.0;
-      const double vt = a.v[i];
-      if (gae) x = (double)a.r[i] + g * (double)a.v[i + N] * nd - vt + gl * nd * x;
-      else x = (double)a.r[i] + g * nd * x;
-      if (window) {
-        a.gz[i] = x;
-        continue;
-      }
-      const double rt = gae ? x + vt : x, ad = gae ? x : x - vt;
-      const float rf = (float)rt, af = (float)ad;
-      a.ret[i] = rf;
-      a.adv[i] = af;
-      m[0] += af; m[1] += (double)af * af; m[2] += rf; m[3] += (double)rf * rf;
-      m[4] += vt; m[5] += vt * vt; m[6] += (double)rf * vt;
-    }
-  }
+  auto emit = [&](size_t i, double rt, double ad, double vt) {   // one fp32 rounding each, then the moments
+    const float rf = (float)rt, af = (float)ad;
+    a.ret[i] = rf;
+    a.adv[i] = af;
+    accum_ret_moments(m, rf, af, vt);
+  };
+  for_chunk_reversed(true, [&](int t, Step s) {
+    const size_t i = (size_t)t * N + n;
+    x = gae ? gae_step(s.r, s.v, s.vn, s.dn, g, gl, x) : nstep_step(s.r, s.dn, g, x);
+    if (window) a.gz[i] = x;
+    else if (gae) emit(i, x + s.v, x, s.v);
+    else emit(i, x, x - s.v, s.v);
+  });
   if (window) {   // uniform across the grid: every thread reaches the barrier
     __syncthreads();   // the later chunks' Gz (same workgroup) are visible
     if (live) {
@@ -398,11 +343,7 @@ __global__ void __launch_bounds__(RS_THREADS) returns_scan_kernel(RetScanArgs a)
           tg += gh * ((double)a.v[(size_t)h * N + n] - (h < T ? a.gz[(size_t)h * N + n] : 0.0));
         }
         const double vt = a.v[i];
-        const float rf = (float)tg, af = (float)(tg - vt);
-        a.ret[i] = rf;
-        a.adv[i] = af;
-        m[0] += af; m[1] += (double)af * af; m[2] += rf; m[3] += (double)rf * rf;
-        m[4] += vt; m[5] += vt * vt; m[6] += (double)rf * vt;
+        emit(i, tg, tg - vt, vt);
       }
     }
   }
@@ -418,19 +359,14 @@ __global__ void __launch_bounds__(RS_THREADS) returns_scan_kernel(RetScanArgs a)
   }
   __syncthreads();
   const double cnt = (double)T * N;
-  const double mean = s_tot[1] / cnt;
-  const double var = fmax(s_tot[2] / cnt - mean * mean, 0.0);
   if (tid == 0) {
     a.mom[0] = cnt;
     for (int k = 0; k < RS_MOM; ++k) a.mom[1 + k] = s_tot[1 + k];
-    if (a.ev_out) {
-      const double mx = s_tot[3] / cnt, my = s_tot[5] / cnt;
-      const double vx = s_tot[4] / cnt - mx * mx, vy = s_tot[6] / cnt - my * my;
-      *a.ev_out = (float)((s_tot[7] / cnt - mx * my) / sqrt(fmax(vx, 0.0) * fmax(vy, 0.0)));
-    }
+    if (a.ev_out) *a.ev_out = ev_corr(s_tot[3], s_tot[4], s_tot[5], s_tot[6], s_tot[7], cnt);
   }
   if (a.norm) {
-    const float fm = (float)mean, inv = 1.0f / (a.eps + (float)sqrt(var));
+    const AdvNorm c = adv_norm(s_tot[1], s_tot[2], cnt, a.eps);
+    const float fm = c.mean, inv = c.inv;
     const int tot = T * N;
     if ((tot & 3) == 0 && (((uintptr_t)a.adv) & 15) == 0) {
       float4* p = reinterpret_cast<float4*>(a.adv);
@@ -462,10 +398,9 @@ __global__ void __launch_bounds__(RS_THREADS) returns_scan_kernel(RetScanArgs a)
 // moments, mom[0] = global count): out = (a - mean) / (eps + std_pop). Elementwise, many workgroups.
 __global__ void normalize_mom_kernel(const float* __restrict__ a, float* __restrict__ out,
                                      const double* __restrict__ mom, int n, float eps) {
-  const double cnt = mom[0], mean = mom[1] / cnt;
-  const double var = fmax(mom[2] / cnt - mean * mean, 0.0);
-  const float fm = (float)mean, inv = 1.0f / (eps + (float)sqrt(var));
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = (a[i] - fm) * inv;
+  const AdvNorm c = adv_norm(mom[1], mom[2], mom[0], eps);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
+    out[i] = (a[i] - c.mean) * c.inv;
 }
 
 // EV correlation over many workgroups: fixed-order partial moments + last-arriver combine (the one-workgroup
@@ -477,10 +412,8 @@ __global__ void __launch_bounds__(RS_THREADS) ev_multi_kernel(const float* __res
   __shared__ double s_tot[5];
   __shared__ int s_flag;
   double m[5] = {0, 0, 0, 0, 0};
-  for (int i = blockIdx.x * RS_THREADS + threadIdx.x; i < n; i += gridDim.x * RS_THREADS) {
-    const double xi = x[i], yi = y[i];
-    m[0] += xi; m[1] += xi * xi; m[2] += yi; m[3] += yi * yi; m[4] += xi * yi;
-  }
+  for (int i = blockIdx.x * RS_THREADS + threadIdx.x; i < n; i += gridDim.x * RS_THREADS)
+    accum_pair_moments(m, x[i], y[i]);
   block_sum_multi<5>(m, sh);
   if (threadIdx.x < 5) part[(size_t)blockIdx.x * 8 + threadIdx.x] = m[threadIdx.x];
   if (!last_block_arrival(ticket, gridDim.x, &s_flag)) return;
@@ -492,11 +425,7 @@ __global__ void __launch_bounds__(RS_THREADS) ev_multi_kernel(const float* __res
       for (int k = 0; k < 5; ++k) s_tot[k] = s[k];
   }
   __syncthreads();
-  if (threadIdx.x == 0) {
-    const double mx = s_tot[0] / n, my = s_tot[2] / n;
-    const double vx = s_tot[1] / n - mx * mx, vy = s_tot[3] / n - my * my;
-    *out = (float)((s_tot[4] / n - mx * my) / sqrt(fmax(vx, 0.0) * fmax(vy, 0.0)));
-  }
+  if (threadIdx.x == 0) *out = ev_corr(s_tot[0], s_tot[1], s_tot[2], s_tot[3], s_tot[4], n);
 }
 
 // Time-limit bootstrap of a fused rollout (mlp.hip mlp_rollout_kernel keeps the terminal observations of truncated

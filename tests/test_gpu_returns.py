@@ -6,7 +6,8 @@ in-kernel returns of ``ac_loss`` (4: staged and unstaged), ``head_bwd`` (5), ``a
 of loss.hip -- for 4-7 only ``ret_w``, ``adv_w`` and the EV in ``stats[7]``; their loss and gradient outputs are
 pinned elsewhere and must merely be finite here. Every element is compared; every tolerance is derived in the oracle
 module's docstring from the kernels' rounding points, none from a kernel output. Each test prints its largest error
-as a fraction of the bound (``pytest -s``). Plus: no entry point accepts a look-ahead below 1.
+as a fraction of the bound (``pytest -s``). Plus: the one-workgroup ``ev`` / ``moments`` / ``normalize`` kernels and
+``mb_gather``'s deferred normalisation against ``stats()`` of their inputs; no entry point accepts a look-ahead below 1.
 """
 import os
 import sys
@@ -305,6 +306,75 @@ def test_ac_loss_fused_returns_match_oracle(cuda, case):
             first = o
         else:
             assert torch.equal(o["adv"], first["adv"]) and torch.equal(o["ret"], first["ret"])
+
+
+# ------------------------------------------------- small statistics: one-workgroup ev / moments / normalize, mb_gather
+
+
+@pytest.mark.parametrize("n", [5, 1025])   # a few threads; one element past the 1024-thread workgroup
+def test_one_workgroup_ev_moments_and_normalize_match_oracle(cuda, n):
+    """``ev_kernel`` (``ops.ev`` without a workspace), ``moments_kernel`` and ``normalize_kernel`` against
+    ``stats()`` of their inputs, with the oracle's ``ev``, ``mom`` and ``norm`` tolerances. ``moments`` returns fp32:
+    its fp64 sum lies within the ``mom`` tolerance of the oracle's and is then rounded once, and rounding is
+    monotonic, so the output must lie between the fp32 roundings of the two ends of that interval."""
+    rng = np.random.default_rng(n)
+    x = rng.standard_normal(n).astype(np.float32)
+    y = (np.float32(0.5) * x + rng.standard_normal(n).astype(np.float32)).astype(np.float32)
+    st = O.stats(x, x, y)   # ret = adv = x, V = y
+    tx, ty = _dev(cuda, x, y)
+    ops = _ops()
+    ev = torch.full((1,), 7.0, device=cuda)
+    ops.ev(tx, ty, ev)
+    _check("ev_kernel", ev, st["ev"], O.tolerance("ev", st=st), "ev")
+    mom = torch.full((5,), 7.0, device=cuda)
+    ops.moments(tx, ty, mom)
+    want, tol = st["mom"][3:8], O.tolerance("mom", st=st)[3:8]   # sum x, x^2, y, y^2, x*y
+    got = mom.cpu().numpy()
+    lo, hi = (want - tol).astype(np.float32), (want + tol).astype(np.float32)
+    print("returns-oracle moments_kernel", got, lo, hi)
+    assert ((lo <= got) & (got <= hi)).all(), ("moments_kernel", got, lo, hi)
+    out = torch.full((n,), 7.0, device=cuda)
+    ops.normalize(tx, out, 1e-8)
+    _check("normalize_kernel", out, st["norm"], O.tolerance("norm", st=st), "norm")
+    assert torch.equal(tx.cpu(), torch.tensor(x)) and torch.equal(ty.cpu(), torch.tensor(y))
+
+
+@pytest.mark.parametrize("index_mode", [True, False], ids=["index", "copy"])
+@pytest.mark.parametrize("R", [16, 20], ids=["vector", "bytes"])   # 16 B vector copies; the byte loop
+def test_mb_gather_deferred_normalisation_matches_oracle(cuda, R, index_mode):
+    """``mb_gather_kernel`` with a ``mom`` tensor (advantage normalisation deferred from the returns scan), both
+    modes: the gather is exact against the keyed permutation of envs/rng.py, the normalised advantages lie within
+    the oracle's ``norm`` tolerance of ``stats()`` of the whole batch. The minibatch ends on the last batch row."""
+    from actor_critic_algs_on_tensorflow_amd.envs import rng as prng
+    n, mb, off, seed, ep = 33, 7, 26, 4242, 1
+    rng = np.random.default_rng(R)
+    obs = torch.tensor(rng.integers(0, 256, (n, R), dtype=np.uint8)).to(cuda)
+    act = torch.tensor(rng.integers(0, 6, n, dtype=np.int32)).to(cuda)
+    logp, adv, ret, v = (rng.standard_normal(n).astype(np.float32) for _ in range(4))
+    adv = (adv * np.float32(3.0) + np.float32(1.0)).astype(np.float32)
+    st = O.stats(ret, adv, v)
+    fl = _dev(cuda, logp, adv, ret, v)
+    mom = torch.tensor(st["mom"][:3], dtype=torch.float64).to(cuda)   # count, sum adv, sum adv^2
+    uc = torch.tensor([3], dtype=torch.int64, device=cuda)
+    o_act = torch.full((mb,), 7, dtype=torch.int32, device=cuda)
+    o_fl = [torch.full((mb,), 7.0, device=cuda) for _ in range(4)]
+    o_obs = None if index_mode else torch.full((mb, R), 7, dtype=torch.uint8, device=cuda)
+    o_idx = torch.full((mb,), -1, dtype=torch.int64, device=cuda) if index_mode else None
+    _ops().mb_gather(obs, act, *fl, o_obs, o_act, *o_fl, seed, uc, ep, off, mom, 1e-8, None, o_idx)
+    torch.cuda.synchronize()
+    sel = prng.prp(torch.arange(off, off + mb, dtype=torch.int64), n, prng.minibatch_key(seed, torch.tensor(3), ep))
+    assert sorted(sel.tolist()) == sorted(set(sel.tolist())) and 0 <= int(sel.min()) and int(sel.max()) < n
+    sel_d = sel.to(cuda)
+    if index_mode:
+        assert torch.equal(o_idx, sel_d)
+    else:
+        assert torch.equal(o_obs, obs[sel_d])
+    assert torch.equal(o_act, act[sel_d])
+    for k in (0, 2, 3):   # logp, ret, old value: copied
+        assert torch.equal(o_fl[k], fl[k][sel_d])
+    s = sel.numpy()
+    _check("mb_gather", o_fl[1], st["norm"][s], O.tolerance("norm", st=st)[s], "norm")
+    assert int(uc) == 3
 
 
 # ------------------------------------------------------------------------------------------------- rejections
