@@ -88,7 +88,9 @@ class Evaluator:
       reward and done is kept in a :class:`RolloutStorage` of its own (``self.storage``). Any other bank or engine
       configuration of a CNN model takes ``"torch"``.
       ``"fused"``: the native MLP engine on the MuJoCo-shaped bank it can roll out in one launch
-      (``engine.supports_fused_rollout``): one ``mlp_rollout_eval`` launch writes the records.
+      (``engine.supports_fused_rollout``): one ``mlp_rollout_eval`` launch writes the records. With
+      ``fused_towers`` (``TrainConfig.fused_rollout_towers``) any other actor whose weights fit in LDS takes the same
+      launch on its generic-tower chain (``engine.supports_rollout_towers``); one that does not fit is ``"native"``.
       ``"native"``: any other bank or tower the native MLP engine takes: ``L x`` (``policy_step(greedy=True)`` +
       ``env.step``) into an ``L``-step :class:`RolloutStorage` of its own (``self.storage``: observations, actions,
       rewards and dones are kept), then one ``eval_scan`` launch.
@@ -106,7 +108,7 @@ class Evaluator:
     host read."""
 
     def __init__(self, model, env, engine=None, obs_norm=None, episodes=1, cuda_graph=False, fused=True,
-                 chunk_steps=64, keep_steps=False):
+                 chunk_steps=64, keep_steps=False, fused_towers=False):
         self.model, self.env, self.engine, self.obs_norm = model, env, engine, obs_norm
         self.episodes = int(episodes)
         if self.episodes < 1:
@@ -121,6 +123,7 @@ class Evaluator:
         self._snap = {k: getattr(env, k).clone() for k in ("state", "t", "tg", "ep_ret")}
         self.obs0 = env.obs.clone()
         self.storage = None
+        self._towers = False   # "fused" on the generic-tower chain
         self.chunk_steps, self.keep_steps = int(chunk_steps), bool(keep_steps)
         chunk_plan(self.L, self.chunk_steps)   # refuses an odd chunk length
         from ..envs.atari import PongVecEnv
@@ -143,6 +146,8 @@ class Evaluator:
                 self._obs = torch.zeros((2, self.N) + tuple(env.obs_shape), dtype=torch.uint8, device=self.device)
         elif fused and engine.supports_fused_rollout(env):
             self.path = "fused"
+        elif fused and fused_towers and engine.supports_rollout_towers(env):
+            self.path, self._towers = "fused", True
         else:
             self.path = "native"
             act_shape = () if env.is_discrete else tuple(env.action_space.shape)
@@ -182,7 +187,7 @@ class Evaluator:
                    rec.cnt.to(torch.float64)], out=self._packed)
 
     def _run_fused(self):
-        self.engine.rollout_eval_linear(self.env, self.obs0, self.L, self.rec)
+        self.engine.rollout_eval_linear(self.env, self.obs0, self.L, self.rec, towers=self._towers)
 
     def _run_native(self):
         st, env, eng = self.storage, self.env, self.engine

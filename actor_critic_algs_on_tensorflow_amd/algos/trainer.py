@@ -276,7 +276,8 @@ class ActorCriticTrainer:
                            max_episode_steps=self.env.max_episode_steps)
             self.evaluator = Evaluator(self.model, ebank, self.mlp if self.mlp is not None else self.engine,
                                        self.obs_norm, cfg.eval_episodes,
-                                       cuda_graph=cfg.cuda_graph, fused=cfg.fused_rollout)
+                                       cuda_graph=cfg.cuda_graph, fused=cfg.fused_rollout,
+                                       fused_towers=cfg.fused_rollout_towers)
         self.iteration = 0
         self.env_steps = 0
         self.graph = None
@@ -526,13 +527,18 @@ class ActorCriticTrainer:
         env bank."""
         st, env, eng = self.storage, self.env, self.mlp
         boot = self.cfg.bootstrap_on_timeout
-        if self.cfg.fused_rollout and eng.supports_fused_rollout(env):
+        fused = self.cfg.fused_rollout and eng.supports_fused_rollout(env)
+        # any other actor whose weights fit in LDS: the same launch on its generic-tower chain, when asked for
+        towers = (not fused and self.cfg.fused_rollout and self.cfg.fused_rollout_towers
+                  and eng.supports_rollout_towers(env))
+        if fused or towers:
             # time-limit bootstrap: the launch keeps the truncated steps' terminal observations in compact slots; one
             # critic launch over the slots and one fix-up launch put gamma * V(terminal observation) into the rewards
             eng.rollout_linear(env, st, KEY_ENV_BITS, self.policy_seed,
                                boot=self._timeout_boot_ws() if boot else None,
                                after_rollout=self._raw_rewards_ready
-                               if self.reward_norm is not None or self.ep_monitor is not None else None)
+                               if self.reward_norm is not None or self.ep_monitor is not None else None,
+                               towers=towers)
             return
         if boot and getattr(self, "_final_obs", None) is None:
             self._final_obs = torch.zeros((st.T,) + tuple(st.obs.shape[1:]), dtype=st.obs.dtype, device=self.device)

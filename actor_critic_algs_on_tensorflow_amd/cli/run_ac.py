@@ -58,6 +58,9 @@ def build_parser():
                    help="activation of the hidden layers of both towers (TrainConfig.hidden_act)")
     p.add_argument("--mlp-init", default=None, choices=["reference", "orthogonal"],
                    help="initialisers of the MLP towers (TrainConfig.mlp_init)")
+    p.add_argument("--fused-rollout-towers", action="store_true",
+                   help="one-launch rollout and evaluation for custom actors whose weights fit in LDS "
+                        "(TrainConfig.fused_rollout_towers; --algo a2c|ppo, MLP models, MuJoCo-shaped bank)")
     return p
 
 
@@ -93,6 +96,8 @@ def config_from_args(a):
         kw["ep_window"] = a.ep_window
     if a.stop_return is not None:
         kw["stop_return"] = a.stop_return
+    if a.fused_rollout_towers:
+        kw["fused_rollout_towers"] = True
     for k in ("actor_hidden", "critic_hidden", "hidden_act", "mlp_init"):
         if getattr(a, k) is not None:
             kw[k] = getattr(a, k)

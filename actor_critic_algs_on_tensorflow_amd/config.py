@@ -212,13 +212,20 @@ class TrainConfig:
     cuda_graph: bool = True
     reuse_rollout_acts: bool = True   # native A2C: the rollout's activations are the learner's forward (exact)
     fused_rollout: bool = True        # native MLP engine + MuJoCo-shaped bank: the whole rollout in one launch
+    # the one-launch rollout (and the one-launch evaluation) for custom actors as well: any tower the native MLP engine
+    # takes, hidden tanh included, whose staged weights fit in LDS (ops/mlp.py MLPEngine.rollout_towers_fit; e.g.
+    # (64, 64), (192, 64), (256, 64, 64) at one frame) runs the launch's generic-tower chain; one that does not fit
+    # ((256, 128)) keeps the per-step rollout. Needs fused_rollout; a2c / ppo on the MLP models; no effect on
+    # engine="torch" or on the reference actor, which keeps its register-resident chain
+    fused_rollout_towers: bool = False
     # -- MLP towers (models/mlp.py) --------------------------------------------------------------------------------
     # hidden widths of the actor / critic (None: the reference's 128-128-64 / 256-128(-128, variant a3c)); the hidden
     # activation of both (None: the reference's lrelu actor / relu critic); the initialisers. A tower is "custom" when
     # its *_hidden or hidden_act is given: 1..4 hidden layers, widths 1..256 (above 32: multiples of 16), at most 256
     # 16 x 16 weight-gradient tiles per tower -- the native MLP engine's limits (check_mlp_tower), checked here for
     # engine "native" / "auto"; engine="torch" has none. a2c / ppo on the MLP models only. Custom towers run the
-    # generic kernels (per-step rollout); the one-launch rollout and the SPEC train path stay the reference's
+    # generic kernels; their rollout is per step unless fused_rollout_towers is set (above), the reference actor's
+    # register-resident one-launch chain and the SPEC train path stay the reference's
     actor_hidden: tuple | None = None
     critic_hidden: tuple | None = None
     hidden_act: str | None = None     # tanh | relu | lrelu
@@ -342,6 +349,13 @@ class TrainConfig:
             if self.model == "cnn":
                 raise ValueError("TrainConfig.actor_hidden / critic_hidden / hidden_act / mlp_init with model='cnn': "
                                  "they configure the MLP towers; the CNN model has none")
+        if self.fused_rollout_towers:
+            if self.algo not in ("a2c", "ppo"):
+                raise ValueError(f"TrainConfig.fused_rollout_towers=True with algo={self.algo!r}: the one-launch "
+                                 "rollout belongs to the a2c / ppo trainer; use a2c or ppo")
+            if self.model == "cnn":
+                raise ValueError("TrainConfig.fused_rollout_towers=True with model='cnn': it selects the rollout of "
+                                 "the MLP towers; the CNN model has none")
         if self.look_ahead is not None and int(self.look_ahead) < 1:
             raise ValueError(f"TrainConfig.look_ahead={self.look_ahead}: must be >= 1 (None = the whole rollout)")
 
@@ -416,6 +430,10 @@ PRESETS = {
 # towers: per-step rollout on the generic kernels, no one-launch rollout)
 PRESETS["halfcheetah_ppo_tanh64"] = dict(PRESETS["mujoco_ppo_dp8"], actor_hidden=(64, 64), critic_hidden=(64, 64),
                                          hidden_act="tanh", mlp_init="orthogonal")
+
+
+# ... and the same with the whole rollout (and evaluation) in one launch on the generic-tower chain
+PRESETS["halfcheetah_ppo_tanh64_fused"] = dict(PRESETS["halfcheetah_ppo_tanh64"], fused_rollout_towers=True)
 
 
 def preset(name, **overrides) -> TrainConfig:

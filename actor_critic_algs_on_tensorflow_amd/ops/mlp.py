@@ -161,6 +161,9 @@ class MLPEngine:
         # evaluate and rollout_linear take RAW observations and normalise them as their input tiles are written;
         # train reads whatever it is given (the trainer feeds it the pre-normalised plane)
         self.obs_norm = None
+        # tests and the microbench only: run every one-launch rollout / evaluation on the generic-tower chain, the
+        # reference actor's too (where it is bitwise equal to the register-resident chain)
+        self._force_rollout_towers = False
         self.sync_shadow()
 
     @staticmethod
@@ -380,21 +383,40 @@ class MLPEngine:
     ROLLOUT_NORM_LDS = 2 * 1024   # static LDS of the NORM instantiations (tables + normalised tile; mlp.hip)
     ROLL_RB = 4   # envs per rollout workgroup (mlp.hip ROLL_RB: 4x4x1 MFMA tiles)
 
-    def rollout_lds_bytes(self, wlds):
-        """Dynamic LDS of mlp_rollout_kernel (layout in mlp.hip); ``wlds`` adds the staged actor weights + biases."""
-        RB = self.ROLL_RB
-        n = 2 * RB * _ld(self.D) + sum(RB * _ld(l.out_features) for l in self.towers[0])
+    @staticmethod
+    def rollout_lds_bytes_of(widths, wlds=True):
+        """Dynamic LDS of mlp_rollout_kernel (layout in mlp.hip) for an actor ``[D, h_0, ..., A]``, from the widths
+        alone (no device, no engine); ``wlds`` adds the staged actor weights + biases."""
+        RB = MLPEngine.ROLL_RB
+        widths = [int(w) for w in widths]
+        n = 2 * RB * _ld(widths[0]) + sum(RB * _ld(w) for w in widths[1:])
         n += LIN_OBS * LIN_OBS + LIN_OBS * LIN_ACT + RB * LIN_OBS + RB * 16
         if wlds:
-            n = (n + 3) // 4 * 4 + sum(l.out_features * _ld(l.in_features) + _ld(l.out_features) - 4
-                                       for l in self.towers[0])
+            n = (n + 3) // 4 * 4 + sum(o * _ld(i) + _ld(o) - 4 for i, o in zip(widths[:-1], widths[1:]))
         return 4 * n
 
-    def rollout_weights_in_lds(self):
-        cap = self.ROLLOUT_MAX_LDS - (self.ROLLOUT_NORM_LDS if self.obs_norm is not None else 0)
-        return self.rollout_lds_bytes(True) <= cap
+    @staticmethod
+    def rollout_towers_fit(widths, norm_obs=False):
+        """Whether the one-launch rollout can hold an actor ``[D, h_0, ..., A]`` (tiles + weights) in LDS: the
+        launcher's cap, less the static tables of the ``norm_obs`` instantiations."""
+        cap = MLPEngine.ROLLOUT_MAX_LDS - (MLPEngine.ROLLOUT_NORM_LDS if norm_obs else 0)
+        return MLPEngine.rollout_lds_bytes_of(widths, True) <= cap
 
-    def rollout_linear(self, env, st, key_shift, seed, stamps=None, boot=None, after_rollout=None):
+    def rollout_lds_bytes(self, wlds):
+        """:meth:`rollout_lds_bytes_of` this engine's actor."""
+        return self.rollout_lds_bytes_of([self.D] + [l.out_features for l in self.towers[0]], wlds)
+
+    def rollout_weights_in_lds(self):
+        return self.rollout_towers_fit([self.D] + [l.out_features for l in self.towers[0]], self.obs_norm is not None)
+
+    def supports_rollout_towers(self, env):
+        """The generic-tower chain of the one-launch rollout (``TrainConfig.fused_rollout_towers``): any actor this
+        engine takes, hidden tanh included, on the MuJoCo-shaped bank, as long as its weights fit in LDS."""
+        from ..envs.mujoco import MujocoShapeVecEnv
+        return (isinstance(env, MujocoShapeVecEnv) and not self.discrete and self.A == LIN_ACT
+                and self.D == LIN_OBS * env.frame_stack and env.frame_stack <= 3 and self.rollout_weights_in_lds())
+
+    def rollout_linear(self, env, st, key_shift, seed, stamps=None, boot=None, after_rollout=None, towers=False):
         """T steps of policy + env for the whole bank in one launch, then V(s) of all (T+1) N observations in one
         critic launch. Equal to T x (:meth:`policy_step` + ``env.step``) + :meth:`value` up to the actor's fp32
         summation order (4x4x1 tiles with the K range split over waves vs 16x16x4 tiles): same RNG keys and resets.
@@ -406,8 +428,13 @@ class MLPEngine:
         ``gamma V(terminal observation)`` to those steps' rewards (unused slots are valued but never read).
 
         ``after_rollout`` (a callable, optional) runs right after the rollout launch, when ``st.rewards`` holds the raw
-        env rewards and before the fix-up launch adds any bootstrap term: the trainer's reward scaling."""
+        env rewards and before the fix-up launch adds any bootstrap term: the trainer's reward scaling.
+
+        ``towers``: the launch runs the generic-tower chain (:meth:`supports_rollout_towers`) instead of the reference
+        actor's register-resident one; everything else about it is the same. On the reference actor the two are
+        bitwise equal, which is what tests select it for."""
         T, N = st.T, env.num_envs
+        towers = bool(towers or self._force_rollout_towers)
         desc, _ = self.desc(None)
         wlds = self.rollout_weights_in_lds()
         if boot is not None and not boot.fits(T, N, self.D, env.max_episode_steps):
@@ -415,12 +442,14 @@ class MLPEngine:
         # observation normaliser: the launch normalises the tile layer 0 reads; st.obs and the slots stay raw, and the
         # critic launches below normalise their own input tiles (_fwd)
         tables, nclip = self.obs_norm.kernel_args() if self.obs_norm is not None else (None, 0.0)
-        _native.require().mlp_rollout(desc, self.rollout_lds_bytes(wlds), st.obs, st.actions, st.logp, st.entropy,
+        _native.require().mlp_rollout(desc, self.rollout_lds_bytes(wlds), st.obs,
+                                      st.actions, st.logp, st.entropy,
                                       st.rewards, st.dones, st.truncated, self.log_std, self.ac_scale, key_shift, seed,
                                       env.state, env.t, env.tg, env.ep_ret, env.ep_stats, env.env_ids, env.A, env.B,
                                       env.seed, env.max_episode_steps, env.frame_stack, wlds, stamps,
                                       None if boot is None else boot.final_obs,
-                                      None if boot is None else boot.final_step, tables, nclip, self.hidden_tanh[0])
+                                      None if boot is None else boot.final_step, tables, nclip, self.hidden_tanh[0],
+                                      self._hdescs[None] if towers else None)
         if after_rollout is not None:
             after_rollout()
         self.value(st.obs.view((T + 1) * N, -1), st.values.view(-1))
@@ -429,13 +458,14 @@ class MLPEngine:
             self.value(boot.final_obs.view(N * boot.S, -1), boot.final_v.view(-1))
             timeout_bootstrap_(st.rewards, boot.final_step, boot.final_v, boot.gamma)
 
-    def rollout_eval_linear(self, env, obs0, steps, rec):
+    def rollout_eval_linear(self, env, obs0, steps, rec, towers=False):
         """Deterministic evaluation of the MuJoCo-shaped bank ``env`` in ONE launch (the ``EVAL`` instantiations of
         ``mlp_rollout_kernel``): ``steps`` steps of actor mean + env step from the first observation stack ``obs0``
         ``[N, D]``; nothing is stored per step, no noise is drawn, and the first ``rec.E`` finished episodes of every
         env go to ``rec`` (an ``ops/evaluation.py`` EvalRecords). The bank's ``state``, ``t``, ``tg`` and ``ep_ret`` are
         advanced and written back; ``ep_stats`` and ``obs0`` are not touched. With an observation normaliser attached
-        layer 0 reads the tile normalised by the tables as they stand."""
+        layer 0 reads the tile normalised by the tables as they stand. ``towers``: as in :meth:`rollout_linear`."""
+        towers = bool(towers or self._force_rollout_towers)
         desc, _ = self.desc(None)
         wlds = self.rollout_weights_in_lds()
         tables, nclip = self.obs_norm.kernel_args() if self.obs_norm is not None else (None, 0.0)
@@ -443,4 +473,4 @@ class MLPEngine:
                                            self.ac_scale, env.state, env.t, env.tg, env.ep_ret, env.env_ids, env.A,
                                            env.B, env.seed, env.max_episode_steps, env.frame_stack, wlds,
                                            rec.ep_ret, rec.ep_len, rec.cnt, tables, nclip, None, None,
-                                           self.hidden_tanh[0])
+                                           self.hidden_tanh[0], self._hdescs[None] if towers else None)

@@ -1303,12 +1303,30 @@ void mlp_epoch_gather(Tensor obs, Tensor act, Tensor logp, Tensor adv, Tensor re
   check(aca_mlp_epoch_gather(&a, cur_stream(obs)), "mlp_epoch_gather");
 }
 
+// Launch of a filled rollout block: through aca_mlp_rollout (the reference actor's register-resident chain), or, when
+// hdesc -- the CPU copy of desc -- is given, through aca_mlp_rollout_towers (the generic-tower chain), which validates
+// the tower and the LDS size from those words. Either launcher's refusal raises before anything is launched.
+static void launch_mlp_rollout(const aca::RolloutArgs& a, int64_t lds, const c10::optional<Tensor>& hdesc,
+                               const Tensor& on, const char* what) {
+  TORCH_CHECK(lds >= 0, "acamd::", what, ": lds must be >= 0");
+  if (!has(hdesc)) {
+    check(aca_mlp_rollout(&a, (size_t)lds, cur_stream(on)), what);
+    return;
+  }
+  TORCH_CHECK(!hdesc->is_cuda() && hdesc->scalar_type() == at::kLong && hdesc->is_contiguous() &&
+                  hdesc->numel() * 8 >= (int64_t)sizeof(aca::MlpTower), "acamd::", what, ": hdesc must be the CPU desc");
+  aca::MlpTower tw;
+  std::memcpy(&tw, hdesc->data_ptr(), sizeof(tw));
+  check(aca_mlp_rollout_towers(&a, &tw, (size_t)lds, cur_stream(on)), what);
+}
+
 void mlp_rollout(Tensor desc, int64_t lds, Tensor obs, Tensor act, Tensor logp, Tensor ent, Tensor reward,
                  Tensor done, Tensor trunc, Tensor log_std, Tensor ac_scale, int64_t key_shift, int64_t policy_seed,
                  Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, Tensor lin_A,
                  Tensor lin_B, int64_t env_seed, int64_t max_steps, int64_t k, bool wlds,
                  c10::optional<Tensor> stamps, c10::optional<Tensor> final_obs, c10::optional<Tensor> final_step,
-                 c10::optional<Tensor> norm_tables, double norm_clip, bool hidden_tanh) {
+                 c10::optional<Tensor> norm_tables, double norm_clip, bool hidden_tanh,
+                 c10::optional<Tensor> hdesc) {
   need(desc, at::kLong, "desc");
   TORCH_CHECK(desc.numel() * 8 >= (int64_t)sizeof(aca::MlpTower), "mlp_rollout: desc too small");
   need(obs, at::kFloat, "obs");
@@ -1386,7 +1404,7 @@ void mlp_rollout(Tensor desc, int64_t lds, Tensor obs, Tensor act, Tensor logp, 
   }
   // the descriptor is device-resident: its owner says whether a hidden layer is tanh (the launcher refuses it)
   a.hidden_tanh = hidden_tanh ? 1 : 0;
-  check(aca_mlp_rollout(&a, (size_t)lds, cur_stream(obs)), "mlp_rollout");
+  launch_mlp_rollout(a, lds, hdesc, obs, "mlp_rollout");
 }
 
 // Deterministic evaluation of the MuJoCo-shaped bank in one launch (the EVAL instantiations of mlp_rollout_kernel):
@@ -1398,7 +1416,7 @@ void mlp_rollout_eval(Tensor desc, int64_t lds, Tensor obs0, int64_t steps, Tens
                       int64_t env_seed, int64_t max_steps, int64_t k, bool wlds, c10::optional<Tensor> rec_ret,
                       c10::optional<Tensor> rec_len, c10::optional<Tensor> rec_cnt,
                       c10::optional<Tensor> norm_tables, double norm_clip, c10::optional<Tensor> final_obs,
-                      c10::optional<Tensor> final_step, bool hidden_tanh) {
+                      c10::optional<Tensor> final_step, bool hidden_tanh, c10::optional<Tensor> hdesc) {
   need(desc, at::kLong, "desc");
   TORCH_CHECK(desc.numel() * 8 >= (int64_t)sizeof(aca::MlpTower), "mlp_rollout_eval: desc too small");
   need(obs0, at::kFloat, "obs0");
@@ -1474,7 +1492,7 @@ void mlp_rollout_eval(Tensor desc, int64_t lds, Tensor obs0, int64_t steps, Tens
     a.norm_clip = (float)norm_clip;
   }
   a.hidden_tanh = hidden_tanh ? 1 : 0;
-  check(aca_mlp_rollout(&a, (size_t)lds, cur_stream(obs0)), "mlp_rollout_eval");
+  launch_mlp_rollout(a, lds, hdesc, obs0, "mlp_rollout_eval");
 }
 
 // ---------------------------------------------------------------------------------------------- evaluation records
@@ -2525,12 +2543,13 @@ TORCH_LIBRARY(acamd, m) {
         "Tensor done, Tensor truncated, Tensor log_std, Tensor ac_scale, int key_shift, int policy_seed, "
         "Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor ep_stats, Tensor env_ids, Tensor lin_A, "
         "Tensor lin_B, int env_seed, int max_steps, int k, bool wlds, Tensor? stamps=None, Tensor? final_obs=None, "
-        "Tensor? final_step=None, Tensor? norm_tables=None, float norm_clip=0.0, bool hidden_tanh=False) -> ()");
+        "Tensor? final_step=None, Tensor? norm_tables=None, float norm_clip=0.0, bool hidden_tanh=False, "
+        "Tensor? hdesc=None) -> ()");
   m.def("mlp_rollout_eval(Tensor desc, int lds, Tensor obs0, int steps, Tensor log_std, Tensor ac_scale, "
         "Tensor state, Tensor t, Tensor tg, Tensor ep_ret, Tensor env_ids, Tensor lin_A, Tensor lin_B, int env_seed, "
         "int max_steps, int k, bool wlds, Tensor? rec_ret, Tensor? rec_len, Tensor? rec_cnt, "
         "Tensor? norm_tables=None, float norm_clip=0.0, Tensor? final_obs=None, Tensor? final_step=None, "
-        "bool hidden_tanh=False) -> ()");
+        "bool hidden_tanh=False, Tensor? hdesc=None) -> ()");
   m.def("eval_scan_unroll() -> int", &eval_scan_unroll);
   m.def("eval_scan(Tensor rewards, Tensor dones, Tensor rec_ret, Tensor rec_len, Tensor rec_cnt) -> ()");
   m.def("obs_norm_parts(int R) -> int", &obs_norm_parts);

@@ -126,6 +126,10 @@ hipError_t aca_mlp_wgrad(const aca::WgradArgs* a, hipStream_t stream);
 hipError_t aca_mlp_epoch_gather(const aca::EpochGatherArgs* a, hipStream_t stream);
 hipError_t aca_mlp_tshadow(const aca::MlpTower* tw, int ntw, int total, hipStream_t stream);
 hipError_t aca_mlp_rollout(const aca::RolloutArgs* a, size_t lds, hipStream_t stream);
+// the same rollout for any actor whose weights fit in LDS (hidden tanh included): tw = the HOST copy of the
+// device-resident descriptor a->tw, which the launcher validates and sizes the LDS from
+hipError_t aca_mlp_rollout_towers(const aca::RolloutArgs* a, const aca::MlpTower* tw, size_t lds,
+                                  hipStream_t stream);
 
 // ---- running observation normalisation (obs_norm.hip)
 int aca_obs_norm_parts(int R);   // partial rows (= workgroups) of aca_obs_norm_prepare over R observation rows

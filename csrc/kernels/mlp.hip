@@ -1608,6 +1608,99 @@ __device__ __forceinline__ void roll_layer_epilogue(const float* __restrict__ re
   }
 }
 
+// ---- the generic-tower chain (GEN instantiations): the same product with every width a run-time value. RollLayer's
+// split is evaluated once per layer at kernel entry (roll_gen_plan) and the weights are read each step from the LDS
+// copy the kernel stages anyway -- no register-resident slice, so no width is a template parameter. Keeping the split
+// keeps the MFMA sequence: on the reference actor this chain and the register chain issue the same instructions on
+// the same operands in the same order, and their rollouts are bitwise equal (tests/test_gpu_rollout_towers.py).
+// Per layer: [0] CG * S (waves that work), [1] kper, [2] CG, [3] S, [4] log2(16 ngp2(N)), then cg | sp << 8 per wave.
+constexpr int GEN_W = 5 + MLP_THREADS / 64;
+__device__ __forceinline__ int* roll_gen_tab() {   // static LDS of the GEN instantiations only
+  __shared__ int tab[MLP_MAXL * GEN_W];
+  return tab;
+}
+
+__device__ __forceinline__ void roll_gen_plan(int* __restrict__ g, int K, int N) {
+  const int K_ = 16 * ngp2(K), NP = 16 * ngp2(N);
+  const int CG = (N + 63) / 64;
+  const int S = MLP_THREADS / 64 / CG < K_ / 4 ? MLP_THREADS / 64 / CG : K_ / 4;
+  g[0] = CG * S;
+  g[1] = K_ / S;
+  g[2] = CG;
+  g[3] = S;
+  g[4] = 31 - __clz(NP);
+  for (int w = 0; w < MLP_THREADS / 64; ++w) g[5 + w] = (w % CG) | ((w / CG) << 8);
+}
+
+// W: the layer's LDS copy [N][ldw] (ldw = K_ + 4); the wave's operands of a k-step are two 16-byte LDS reads
+__device__ __forceinline__ void roll_gen_mfma(const int* __restrict__ g, const float* __restrict__ W, int ldw, int N,
+                                              const float* __restrict__ X, int ldx, float* __restrict__ red) {
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (wave < __builtin_amdgcn_readfirstlane(g[0])) {
+    const int kper = __builtin_amdgcn_readfirstlane(g[1]);
+    const int cs = __builtin_amdgcn_readfirstlane(g[5 + wave]);
+    const int cg = cs & 255, sp = cs >> 8;
+    const int c = min(cg * 64 + lane, N - 1);
+    const float* wr = W + c * ldw + sp * kper;
+    const float* xr = X + (lane & 3) * ldx + sp * kper;
+    floatx4 acc = {0.f, 0.f, 0.f, 0.f};
+    // kper / 4 is a power of two: rounds of four float4 pairs (eight LDS reads in flight ahead of their sixteen
+    // MFMAs), then at most two single pairs -- always in ascending k, the register chain's order
+    int k = 0;
+    for (; k + 16 <= kper; k += 16) {
+      float4 x[4], w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        x[u] = *reinterpret_cast<const float4*>(xr + k + 4 * u);
+        w[u] = *reinterpret_cast<const float4*>(wr + k + 4 * u);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc = mfma4x4(x[u].x, w[u].x, acc);
+        acc = mfma4x4(x[u].y, w[u].y, acc);
+        acc = mfma4x4(x[u].z, w[u].z, acc);
+        acc = mfma4x4(x[u].w, w[u].w, acc);
+      }
+    }
+    for (; k < kper; k += 4) {
+      const float4 x = *reinterpret_cast<const float4*>(xr + k);
+      const float4 w = *reinterpret_cast<const float4*>(wr + k);
+      acc = mfma4x4(x.x, w.x, acc);
+      acc = mfma4x4(x.y, w.y, acc);
+      acc = mfma4x4(x.z, w.z, acc);
+      acc = mfma4x4(x.w, w.w, acc);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[(wave * 4 + i) * 64 + lane] = acc[i];
+  }
+}
+
+// partial tiles summed in split order, + bias, activation (a hidden tanh layer is tanhf(sum + bias) as in layer_fwd_t:
+// the code is uniform over the layer, a scalar branch), zero pad columns [N, 16 ngp2(N))
+__device__ __forceinline__ void roll_gen_epilogue(const int* __restrict__ g, const float* __restrict__ red,
+                                                  const float* __restrict__ bias, int N, int act,
+                                                  float* __restrict__ Y, int ldy) {
+  const int CG = __builtin_amdgcn_readfirstlane(g[2]), S = __builtin_amdgcn_readfirstlane(g[3]);
+  const int lg = __builtin_amdgcn_readfirstlane(g[4]);
+  const float slope = act_slope(act);
+  auto run = [&](auto tanh_act) {
+    for (int e = threadIdx.x; e < (ROLL_RB << lg); e += MLP_THREADS) {
+      const int i = e >> lg, c = e & ((1 << lg) - 1);
+      float v = 0.f;
+      if (c < N) {
+        const int cg = c >> 6, l = c & 63;
+        float sum = 0.f;
+        for (int sp = 0; sp < S; ++sp) sum += red[((sp * CG + cg) * 4 + i) * 64 + l];
+        if constexpr (decltype(tanh_act)::value) v = tanhf(sum + bias[c]);
+        else v = act_fwd(sum + bias[c], slope);
+      }
+      Y[i * ldy + c] = v;
+    }
+  };
+  if (__builtin_amdgcn_readfirstlane(act) == ACT_TANH) run(std::true_type{});
+  else run(std::false_type{});
+}
+
 // The actor's weights and biases are staged in LDS once (the reference actor at D = 17 is ~120 KB, SURVEY §2.4 K01;
 // ops/mlp.py takes this kernel only when they fit), so the step loop issues no global loads at all. That matters
 // beyond the load latency: on gfx9 global stores count on vmcnt too, so every wait for a load issued after the
@@ -1627,7 +1720,10 @@ __device__ __forceinline__ void roll_layer_epilogue(const float* __restrict__ re
 // when an env finishes an episode -- the owner lane then writes the episode's return and length (s_er / s_t, the
 // bank's own accumulators) into the env's next record slot (s_ne counts them). a.obs is the first observation stack
 // [N][D] only. The bank write-back is the same and also writes the counts.
-template <int KP0, bool BOOT, bool NORM, bool EVAL = false>
+// GEN: the generic-tower chain (roll_gen_*; aca_mlp_rollout_towers): any actor of up to MLP_MAXL layers whose weights
+// fit in LDS, hidden tanh included. Always KP0 = 64 -- the widest padded stack, which sizes the NORM tables; the
+// frame count is a.k. Everything outside the actor chain is the code of the other instantiations.
+template <int KP0, bool BOOT, bool NORM, bool EVAL = false, bool GEN = false>
 __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // 16-byte base: the b128 LDS reads stay aligned
   __shared__ int64_t s_tg[ROLL_RB];
@@ -1747,11 +1843,15 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
   using L1 = RollLayer<128, 128>;
   using L2 = RollLayer<128, 64>;
   using L3 = RollLayer<64, 16>;
-  float4 w0[L0::NU], w1[L1::NU], w2[L2::NU], w3[L3::NU];
-  roll_layer_load_w<L0>(w0, sm + s_wo[0], KP0 + 4, s_out[0]);
-  roll_layer_load_w<L1>(w1, sm + s_wo[1], 132, s_out[1]);
-  roll_layer_load_w<L2>(w2, sm + s_wo[2], 132, s_out[2]);
-  roll_layer_load_w<L3>(w3, sm + s_wo[3], 68, s_out[3]);
+  [[maybe_unused]] float4 w0[L0::NU], w1[L1::NU], w2[L2::NU], w3[L3::NU];
+  if constexpr (GEN) {   // the layers' wave splits, once (lane l < nl plans layer l; read after the barrier below)
+    if (tid < nl) roll_gen_plan(roll_gen_tab() + tid * GEN_W, s_in[tid], s_out[tid]);
+  } else {
+    roll_layer_load_w<L0>(w0, sm + s_wo[0], KP0 + 4, s_out[0]);
+    roll_layer_load_w<L1>(w1, sm + s_wo[1], 132, s_out[1]);
+    roll_layer_load_w<L2>(w2, sm + s_wo[2], 132, s_out[2]);
+    roll_layer_load_w<L3>(w3, sm + s_wo[3], 68, s_out[3]);
+  }
   auto bias_of = [&](int l, int ldw) { return sm + s_wo[l] + s_out[l] * ldw; };
   // The policy noise of step t depends only on (seed, env counter, env id, component): waves 2 and 4 (idle during the
   // env step) compute step t + 1's two Box-Muller factors while waves 0-1 step the envs -- wave 2 sqrt(-2 log u1),
@@ -1782,32 +1882,55 @@ __global__ void __launch_bounds__(MLP_THREADS) mlp_rollout_kernel(RolloutArgs a)
     float* Xc = sm + (step & 1) * ROLL_RB * ld0;
     float* Xn = sm + ((step & 1) ^ 1) * ROLL_RB * ld0;
     // ---- actor forward
-    float* Y0 = sm + s_yo[0];
-    float* Y1 = sm + s_yo[1];
-    float* Y2 = sm + s_yo[2];
-    float* Y3 = sm + s_yo[3];
-    roll_layer_mfma<L0>(w0, NORM ? s_xq : Xc, ld0, s_red);
-    __syncthreads();
-    roll_layer_epilogue<L0>(s_red, bias_of(0, KP0 + 4), s_out[0], s_actc[0], Y0, 132);
-    __syncthreads();
-    stamp(step, 0);
-    roll_layer_mfma<L1>(w1, Y0, 132, s_red);
-    __syncthreads();
-    roll_layer_epilogue<L1>(s_red, bias_of(1, 132), s_out[1], s_actc[1], Y1, 132);
-    __syncthreads();
-    stamp(step, 1);
-    roll_layer_mfma<L2>(w2, Y1, 132, s_red);
-    __syncthreads();
-    roll_layer_epilogue<L2>(s_red, bias_of(2, 132), s_out[2], s_actc[2], Y2, 68);
-    __syncthreads();
-    stamp(step, 2);
-    roll_layer_mfma<L3>(w3, Y2, 68, s_red);
-    __syncthreads();
-    roll_layer_epilogue<L3>(s_red, bias_of(3, 68), s_out[3], s_actc[3], Y3, 20);
-    __syncthreads();
-    stamp(step, 3);
-    const float* X = Y3;
-    const int ldx = 20;
+    const float* X;
+    int ldx;
+    if constexpr (GEN) {
+      const int* gt = roll_gen_tab();
+      const float* Xl = NORM ? s_xq : Xc;
+      int ldl = ld0;
+      for (int l = 0; l < nl; ++l) {
+        const int N = __builtin_amdgcn_readfirstlane(s_out[l]), ldw = ldl, ldy = ld_of(N);   // ldw = 16 ngp2(in) + 4
+        const float* Wp = sm + __builtin_amdgcn_readfirstlane(s_wo[l]);
+        float* Yl = sm + __builtin_amdgcn_readfirstlane(s_yo[l]);
+        roll_gen_mfma(gt + l * GEN_W, Wp, ldw, N, Xl, ldl, s_red);
+        __syncthreads();
+        // (the top layer stores z whatever its code says: the head below applies the Gaussian mean's tanh itself)
+        roll_gen_epilogue(gt + l * GEN_W, s_red, Wp + N * ldw, N, l + 1 < nl ? s_actc[l] : (int)ACT_NONE, Yl, ldy);
+        __syncthreads();
+        stamp(step, l);
+        Xl = Yl;
+        ldl = ldy;
+      }
+      X = Xl;
+      ldx = ldl;
+    } else {
+      float* Y0 = sm + s_yo[0];
+      float* Y1 = sm + s_yo[1];
+      float* Y2 = sm + s_yo[2];
+      float* Y3 = sm + s_yo[3];
+      roll_layer_mfma<L0>(w0, NORM ? s_xq : Xc, ld0, s_red);
+      __syncthreads();
+      roll_layer_epilogue<L0>(s_red, bias_of(0, KP0 + 4), s_out[0], s_actc[0], Y0, 132);
+      __syncthreads();
+      stamp(step, 0);
+      roll_layer_mfma<L1>(w1, Y0, 132, s_red);
+      __syncthreads();
+      roll_layer_epilogue<L1>(s_red, bias_of(1, 132), s_out[1], s_actc[1], Y1, 132);
+      __syncthreads();
+      stamp(step, 1);
+      roll_layer_mfma<L2>(w2, Y1, 132, s_red);
+      __syncthreads();
+      roll_layer_epilogue<L2>(s_red, bias_of(2, 132), s_out[2], s_actc[2], Y2, 68);
+      __syncthreads();
+      stamp(step, 2);
+      roll_layer_mfma<L3>(w3, Y2, 68, s_red);
+      __syncthreads();
+      roll_layer_epilogue<L3>(s_red, bias_of(3, 68), s_out[3], s_actc[3], Y3, 20);
+      __syncthreads();
+      stamp(step, 3);
+      X = Y3;
+      ldx = 20;
+    }
     if (layers_only) {
       stamp(step, 6);
       continue;
@@ -2061,28 +2184,36 @@ constexpr size_t ROLLOUT_MAX_LDS = 150 * 1024;   // + ~9 KB static (s_red): with
 // the NORM instantiations hold their tables and normalised tile in static LDS too (1.6 KB at KP0 = 64)
 constexpr size_t ROLLOUT_NORM_LDS = 2 * 1024;
 
-extern "C" hipError_t aca_mlp_rollout(const RolloutArgs* a, size_t lds, hipStream_t stream) {
-  if (a->N <= 0 || a->T <= 0) return hipSuccess;
+// What both rollout launchers ask of the argument block (the actor's shape is each launcher's own business); boot,
+// norm and eval select the instantiation.
+static bool rollout_args_ok(const RolloutArgs* a, bool& boot, bool& norm, bool& eval) {
   if (!a->tw || a->head != 2 || a->A != LIN_ACT || a->k < 1 || a->k > 3 || a->D != LIN_OBS * a->k || !a->wlds)
-    return hipErrorInvalidValue;
-  if (a->hidden_tanh) return hipErrorInvalidValue;   // slope activations only (relu / lrelu / identity)
+    return false;
   // terminal observations: an env that enters with t < max_steps truncates at most ceil(T / max_steps) times
-  const bool boot = a->final_obs != nullptr;
+  boot = a->final_obs != nullptr;
   if (boot && (!a->final_step || a->max_steps < 1 ||
                (int64_t)a->S * a->max_steps < (int64_t)a->T))   // S < ceil(T / max_steps)
-    return hipErrorInvalidValue;
+    return false;
   // observation normalisation: both tables or none
-  const bool norm = a->norm_mean != nullptr;
-  if (norm != (a->norm_istd != nullptr)) return hipErrorInvalidValue;
+  norm = a->norm_mean != nullptr;
+  if (norm != (a->norm_istd != nullptr)) return false;
   // deterministic evaluation (the record pointer selects it): records instead of storage, never with the bootstrap's
   // slots; every other launch needs all of its storage
-  const bool eval = a->ev_ret != nullptr;
-  if (eval && (boot || !a->ev_len || !a->ev_cnt || a->E < 1 || !a->obs)) return hipErrorInvalidValue;
+  eval = a->ev_ret != nullptr;
+  if (eval && (boot || !a->ev_len || !a->ev_cnt || a->E < 1 || !a->obs)) return false;
   if (!eval && (!a->obs || !a->act || !a->logp || !a->ent || !a->reward || !a->done || !a->trunc))
-    return hipErrorInvalidValue;
+    return false;
   if (!a->state || !a->t || !a->tg || !a->ep_ret || !a->env_ids || !a->lin_A || !a->lin_B || !a->log_std ||
       !a->ac_scale || (!eval && !a->ep_stats))
-    return hipErrorInvalidValue;
+    return false;
+  return true;
+}
+
+extern "C" hipError_t aca_mlp_rollout(const RolloutArgs* a, size_t lds, hipStream_t stream) {
+  if (a->N <= 0 || a->T <= 0) return hipSuccess;
+  if (a->hidden_tanh) return hipErrorInvalidValue;   // slope activations only (relu / lrelu / identity)
+  bool boot, norm, eval;
+  if (!rollout_args_ok(a, boot, norm, eval)) return hipErrorInvalidValue;
   const dim3 grid((a->N + ROLL_RB - 1) / ROLL_RB);
   if (eval) {
     static bool eattr = false;
@@ -2133,6 +2264,58 @@ extern "C" hipError_t aca_mlp_rollout(const RolloutArgs* a, size_t lds, hipStrea
     case 5: mlp_rollout_kernel<64, false, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
     case 6: mlp_rollout_kernel<32, true, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
     default: mlp_rollout_kernel<64, true, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+  }
+  return hipGetLastError();
+}
+
+// The one-launch rollout of ANY actor whose weights fit in LDS (the GEN instantiations). The device-resident
+// descriptor cannot be read here, so the caller also passes its host copy `tw` (the same words, ops/mlp.py keeps
+// both): the tower's shape is validated from it and the dynamic LDS the kernel's layout needs for it is computed
+// here -- a launch with fewer bytes than that, or more than the cap, is refused before anything runs.
+extern "C" hipError_t aca_mlp_rollout_towers(const RolloutArgs* a, const MlpTower* tw, size_t lds,
+                                             hipStream_t stream) {
+  if (a->N <= 0 || a->T <= 0) return hipSuccess;
+  bool boot, norm, eval;
+  if (!tw || !rollout_args_ok(a, boot, norm, eval)) return hipErrorInvalidValue;
+  if (tw->nl < 1 || tw->nl > MLP_MAXL) return hipErrorInvalidValue;
+  const int nl = (int)tw->nl;
+  // LDS: obs tile x2 | Y_l | A | B | env state | actions | (16-byte aligned) W_l, b_l  (mlp_rollout_kernel)
+  size_t tiles = 2 * ROLL_RB * (16 * mlp_ngp2(a->D) + 4), weights = 0;
+  for (int l = 0; l < nl; ++l) {
+    const int64_t K = tw->in[l], N = tw->out[l];
+    if (K < 1 || K > MLP_MAXW || N < 1 || N > MLP_MAXW || K != (l ? tw->out[l - 1] : (int64_t)a->D))
+      return hipErrorInvalidValue;
+    if (tw->act[l] < ACT_NONE || tw->act[l] > ACT_TANH || !tw->F[l] || !tw->b[l]) return hipErrorInvalidValue;
+    tiles += ROLL_RB * (16 * mlp_ngp2((int)N) + 4);
+    weights += N * (16 * mlp_ngp2((int)K) + 4) + 16 * mlp_ngp2((int)N);
+  }
+  if (tw->out[nl - 1] != a->A) return hipErrorInvalidValue;
+  tiles += LIN_OBS * LIN_OBS + LIN_OBS * LIN_ACT + ROLL_RB * LIN_OBS + ROLL_RB * MLP_MAXA;
+  const size_t need = 4 * (((tiles + 3) & ~(size_t)3) + weights);
+  if (lds < need || lds > ROLLOUT_MAX_LDS - (norm ? ROLLOUT_NORM_LDS : 0)) return hipErrorInvalidValue;
+  // the six combinations of the other launcher: (BOOT, NORM) and, for EVAL, NORM
+  const void* ks[6] = {reinterpret_cast<const void*>(&mlp_rollout_kernel<64, false, false, false, true>),
+                       reinterpret_cast<const void*>(&mlp_rollout_kernel<64, true, false, false, true>),
+                       reinterpret_cast<const void*>(&mlp_rollout_kernel<64, false, true, false, true>),
+                       reinterpret_cast<const void*>(&mlp_rollout_kernel<64, true, true, false, true>),
+                       reinterpret_cast<const void*>(&mlp_rollout_kernel<64, false, false, true, true>),
+                       reinterpret_cast<const void*>(&mlp_rollout_kernel<64, false, true, true, true>)};
+  static bool attr = false;
+  if (!attr) {
+    for (int i = 0; i < 6; ++i)
+      if (hipFuncSetAttribute(ks[i], hipFuncAttributeMaxDynamicSharedMemorySize,
+                              ROLLOUT_MAX_LDS - (i == 2 || i == 3 || i == 5 ? ROLLOUT_NORM_LDS : 0)) != hipSuccess)
+        return hipErrorInvalidValue;
+    attr = true;
+  }
+  const dim3 grid((a->N + ROLL_RB - 1) / ROLL_RB);
+  switch (eval ? 4 + (norm ? 1 : 0) : (norm ? 2 : 0) | (boot ? 1 : 0)) {
+    case 0: mlp_rollout_kernel<64, false, false, false, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    case 1: mlp_rollout_kernel<64, true, false, false, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    case 2: mlp_rollout_kernel<64, false, true, false, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    case 3: mlp_rollout_kernel<64, true, true, false, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    case 4: mlp_rollout_kernel<64, false, false, true, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
+    default: mlp_rollout_kernel<64, false, true, true, true><<<grid, MLP_THREADS, lds, stream>>>(*a); break;
   }
   return hipGetLastError();
 }

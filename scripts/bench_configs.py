@@ -4,7 +4,7 @@
     python scripts/bench_configs.py [--configs pong_a2c,breakout_ppo,mujoco_ppo_dp8,cartpole_cpu] [--updates K]
                                     [--warmup W] [--engine auto|torch] [--device cuda:0] [--engine-opts JSON]
                                     [--bootstrap-on-timeout] [--norm-obs] [--norm-reward]
-                                    [--target-kl X] [--ep-window K]
+                                    [--target-kl X] [--ep-window K] [--fused-rollout-towers]
 
 Each config runs with its preset (config.py PRESETS): same model, env bank, rollout length, optimiser and PPO
 epochs/minibatches as BASELINE.json names; synthetic envs and random-init weights. The update is captured as a
@@ -26,7 +26,7 @@ import torch  # noqa: E402
 
 
 def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None, bootstrap_on_timeout=False,
-        norm_obs=False, norm_reward=False, target_kl=None, ep_window=0):
+        norm_obs=False, norm_reward=False, target_kl=None, ep_window=0, fused_rollout_towers=False):
     from actor_critic_algs_on_tensorflow_amd import preset
     from actor_critic_algs_on_tensorflow_amd.algos.trainer import ActorCriticTrainer
     dev = device if name != "cartpole_cpu" or device == "cpu" else device
@@ -42,6 +42,8 @@ def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None
         cfg = cfg.replace(target_kl=target_kl)   # (validated: PPO configs only; a CNN config runs on the torch engine)
     if ep_window:
         cfg = cfg.replace(ep_window=ep_window)   # (the rolling episode window: two launches per update)
+    if fused_rollout_towers:
+        cfg = cfg.replace(fused_rollout_towers=True)   # (validated: MLP configs only; custom actors that fit LDS)
     if engine_opts:
         import dataclasses
         cfg.engine_opts = dataclasses.replace(cfg.engine_opts, **engine_opts)
@@ -81,10 +83,12 @@ def run(name, updates, warmup, engine, device, dp_world1=False, engine_opts=None
             "hipgraph": bool(tr.graph), "device": dev, "dp_world1": bool(dp_world1),
             "engine_opts": engine_opts or {}, "bootstrap_on_timeout": bool(cfg.bootstrap_on_timeout),
             "norm_obs": bool(cfg.norm_obs), "norm_reward": bool(cfg.norm_reward), "ep_window": int(cfg.ep_window),
+            "fused_rollout_towers": bool(cfg.fused_rollout_towers),
             "ppo": {"epochs": cfg.ppo_epochs, "minibatches": cfg.ppo_minibatches} if cfg.algo == "ppo" else None}
 
 
-def run_eval(name, reps, device, norm_obs=False, eval_envs=16, eval_episodes=1, max_episode_steps=None, opts=None):
+def run_eval(name, reps, device, norm_obs=False, eval_envs=16, eval_episodes=1, max_episode_steps=None, opts=None,
+             fused_rollout_towers=False):
     """The deterministic evaluation of a config (``TrainConfig.eval_every``; algos/evaluator.py) on its own: time per
     evaluation as its captured graph replays (restore, launches, summary; the CNN path: its chain of chunk graphs),
     and, as the yardstick, the training rollout (``collect``) timed eagerly on the same trainer.
@@ -94,6 +98,8 @@ def run_eval(name, reps, device, norm_obs=False, eval_envs=16, eval_episodes=1, 
     from actor_critic_algs_on_tensorflow_amd.algos.trainer import ActorCriticTrainer
     cuda = device.startswith("cuda")
     kw = dict(engine_opts=opts) if opts else {}
+    if fused_rollout_towers:
+        kw["fused_rollout_towers"] = True
     cfg = preset(name, device=device, outdir=None, quiet=True, stdout_freq=0, save_every=0, cuda_graph=cuda,
                  eval_every=1, eval_envs=eval_envs, eval_episodes=eval_episodes, norm_obs=norm_obs, **kw)
     env = None
@@ -121,7 +127,8 @@ def run_eval(name, reps, device, norm_obs=False, eval_envs=16, eval_episodes=1, 
     tr.collect()
     dt_roll = timed(tr.collect, max(1, reps // 2))
     return {"config": name, "eval": True, "path": ev.path, "hipgraph": ev.graph is not None, "device": device,
-            "norm_obs": bool(norm_obs), "eval_envs": ev.N, "eval_steps": ev.L, "ms_per_eval": round(1e3 * dt, 4),
+            "norm_obs": bool(norm_obs), "fused_rollout_towers": bool(cfg.fused_rollout_towers), "eval_envs": ev.N,
+            "eval_steps": ev.L, "ms_per_eval": round(1e3 * dt, 4),
             "us_per_eval_step": round(1e6 * dt / ev.L, 3), "ret_mean": res["ret_mean"], "episodes": res["episodes"],
             "train_rollout_envs": tr.env.num_envs, "train_rollout_steps": cfg.n_steps,
             "train_collect_ms": round(1e3 * dt_roll, 4), "train_collect_us_per_step": round(1e6 * dt_roll / cfg.n_steps, 3)}
@@ -150,6 +157,8 @@ def main():
                     help="set TrainConfig.target_kl on the chosen configs (PPO; early stopping on the approximate KL)")
     ap.add_argument("--ep-window", type=int, default=0,
                     help="set TrainConfig.ep_window on the chosen configs (the rolling window over the last K episodes)")
+    ap.add_argument("--fused-rollout-towers", action="store_true",
+                    help="set TrainConfig.fused_rollout_towers on the chosen configs (MLP models; also under --eval)")
     ap.add_argument("--eval", action="store_true",
                     help="measure the deterministic evaluation (eval_every) of the chosen configs (the MLP presets and "
                          "pong_a2c / breakout_ppo) instead of their updates: --updates replays of the evaluation graph "
@@ -162,12 +171,14 @@ def main():
     if args.eval:
         for name in args.configs.split(","):
             res = run_eval(name, args.updates, args.device, args.norm_obs, args.eval_envs,
-                           max_episode_steps=args.eval_max_steps, opts=opts)
+                           max_episode_steps=args.eval_max_steps, opts=opts,
+                           fused_rollout_towers=args.fused_rollout_towers)
             os.write(out_fd, (json.dumps(res) + "\n").encode())
         return
     for name in args.configs.split(","):
         res = run(name, args.updates, args.warmup, args.engine, args.device, args.dp_world1, opts,
-                  args.bootstrap_on_timeout, args.norm_obs, args.norm_reward, args.target_kl, args.ep_window)
+                  args.bootstrap_on_timeout, args.norm_obs, args.norm_reward, args.target_kl, args.ep_window,
+                  args.fused_rollout_towers)
         os.write(out_fd, (json.dumps(res) + "\n").encode())
 
 
